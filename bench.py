@@ -144,7 +144,11 @@ def main():
     ap.add_argument("--workload", choices=("cfg2", "cfg3"), default="cfg2")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous rehearsal without a GPU (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (seeded sample, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))       # (no GPU call has been made in this process)
@@ -338,6 +342,8 @@ def main():
     timer = Timer(dist, torch.cuda.synchronize)
     elapsed = timer.measure(timed_steps)
     assert int(wl.over.item()) == 0, "synthetic audio must not overflow float32 storage"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl, wl.cur, rank, world)
 
     enc_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_enc]))
     dec_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_dec]))
@@ -451,6 +457,61 @@ def main():
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60_000_000                  # --dump-outputs: all ranks' .npy data together (< 64 MB with headers)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(out_dir: str, wl, d: dict, rank: int, world: int) -> None:
+    """--dump-outputs DIR: what the last timed step handed its caller, as .npy files a second build can be compared with.
+      absmax         float64 [frames]              per-frame max |x| from the encode (full frames, then the tails)
+      payload        float32 [rows, N*C]           the encoded frames, 32-bit big-endian words read as float32
+      decoded        float64 [rows, N, C]          the decoded PCM of the same frames (cfg3: [clips, 48000, C], whole clips)
+      payload_tail / decoded_tail                  the same for the short tail frames
+      sample_index   float64 [rows]                which frames (cfg2) or clips (cfg3) the sampled arrays hold
+    The full output is ~0.7 GB, so whole frames / clips are sampled: a fixed seed picks the same ones on every run.  With
+    several ranks, rank r writes <name>.rank<r>.npy and the budget is split between the ranks."""
+    import numpy as np
+    import torch
+
+    def words(pay):                                           # uint8 rows of BE float32 words -> float32 values
+        return pay.cpu().numpy().view(">f4").astype(np.float32)
+
+    tail_pay = d.get("pay_t")
+    fixed = d["absmax_all"].numel() * 8
+    if wl.gather:                                             # cfg3: whole clips, every frame of a clip in place
+        n_units = wl.n_clips
+        per_unit = wl.full_per_clip * d["pay"].shape[1] + (tail_pay.shape[1] if wl.tail else 0) + wl.clip_len * CHANNELS * 8
+    else:                                                     # cfg2: full frames; the tail frame is always written whole
+        n_units = wl.n_full
+        per_unit = d["pay"].shape[1] + FSIZE * CHANNELS * 8
+        if wl.tail:
+            fixed += tail_pay.numel() + d["out_t"].numel() * 8
+    k = int(min(n_units, (DUMP_BYTES // world - fixed) // (per_unit + 8)))
+    assert k >= 1, "--dump-outputs: the fixed outputs alone exceed the budget"
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_units, size=k, replace=False))
+    sel = torch.from_numpy(pick).to(d["pay"].device)
+    out = {"absmax": d["absmax_all"].cpu().numpy(), "sample_index": pick.astype(np.float64)}
+    if wl.gather:
+        rows = (sel[:, None] * wl.full_per_clip + torch.arange(wl.full_per_clip, device=sel.device)).reshape(-1)
+        out["payload"] = words(d["pay"].index_select(0, rows))
+        out["decoded"] = d["out_clips"].index_select(0, sel).cpu().numpy()
+        if wl.tail:
+            out["payload_tail"] = words(tail_pay.index_select(0, sel))
+    else:
+        out["payload"] = words(d["pay"].index_select(0, sel))
+        out["decoded"] = d["out"].index_select(0, sel).cpu().numpy()
+        if wl.tail:
+            out["payload_tail"] = words(tail_pay)
+            out["decoded_tail"] = d["out_t"].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    print(f"bench.py: wrote {', '.join(out)} ({sum(a.nbytes for a in out.values()) / 2**20:.1f} MiB, {k} of {n_units} "
+          f"{'clips' if wl.gather else 'frames'}) to {out_dir}", file=sys.stderr, flush=True)
 
 
 def wl_samples_total(workload, world, srate, seconds, channels):
