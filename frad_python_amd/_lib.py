@@ -52,6 +52,9 @@ SYMBOLS = {
     "frad_p4_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
     "frad_p1_digital_pcm": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
     "frad_asfh_scan": (c_int64, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frad_rs_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_rs_repair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "frad_bench_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
@@ -188,6 +191,13 @@ class FradLib:
         if rows < 0:
             self._check(int(rows))
         return table[:rows], int(nxt.value), int(why.value)
+
+    def rs_encode(self, data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, stream=0):
+        self._check(self.dll.frad_rs_encode(data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, stream))
+
+    def rs_repair(self, data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected, failed, work, stream=0):
+        self._check(self.dll.frad_rs_repair(data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected,
+                                            failed, work, stream))
 
     def bench_copy(self, src, dst, nbytes, stream=0):
         self._check(self.dll.frad_bench_copy(src, dst, nbytes, stream))

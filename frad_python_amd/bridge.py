@@ -173,3 +173,66 @@ class HipBridge:
         pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
         out, nxt = self.core.p1_overlap_add(t.from_numpy(np.ascontiguousarray(frames)).to(self.device), ratio, pt)
         return out.cpu().numpy(), nxt.cpu().numpy()
+
+    # ------------------------------------------------------------------ Reed-Solomon (csrc/frad_ecc.hip)
+    def _rs_upload(self, payloads, dsize, codesize, repair):
+        from . import ecc
+        buf, head, n_blocks, out_off = ecc.pack(payloads, dsize, codesize, repair)
+        dev = self.torch.from_numpy(buf).to(self.device)                  # payloads + the three offset arrays: one H2D copy
+        n1 = len(payloads) + 1
+        p = dev.data_ptr()
+        return dev, (p, p + head, p + head + 8 * n1, p + head + 16 * n1), n_blocks, out_off
+
+    def rs_encode(self, payloads: list, dsize: int, codesize: int, crc32: bool = False):
+        """ecc.encode(p, dsize, codesize) of every payload (tools/ecc.py:6-12): one upload, one launch, one download.
+        With ``crc32`` also zlib.crc32 of every protected payload, computed on the device (frad_crc32_frames over each run
+        of equally long outputs): -> (outputs, crcs)."""
+        t = self.torch
+        lib = self.core._lib.load()
+        n = len(payloads)
+        if n == 0:
+            return ([], []) if crc32 else []
+        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, False)
+        nout = int(out_off[-1])
+        out = t.empty(max((nout + 15) // 16 * 16, 16), dtype=t.uint8, device=self.device)
+        stream = int(t.cuda.current_stream(self.device).cuda_stream)
+        with t.cuda.device(self.device):
+            lib.rs_encode(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), stream)
+            crcs = None
+            if crc32:
+                lens = np.diff(out_off)
+                crc_dev = t.zeros(n, dtype=t.int32, device=self.device)
+                i = 0
+                while i < n:                                              # runs of equal length: one launch each
+                    j = i + 1
+                    while j < n and lens[j] == lens[i]:
+                        j += 1
+                    lib.crc32_frames(out.data_ptr() + int(out_off[i]), int(lens[i]), j - i, int(lens[i]),
+                                     crc_dev.data_ptr() + 4 * i, stream)
+                    i = j
+                crcs = crc_dev.cpu().numpy().view(np.uint32).tolist()
+        host = self._down_bytes(out[:nout]) if nout else b""
+        outs = [host[out_off[i]:out_off[i + 1]] for i in range(n)]
+        del dev
+        return (outs, crcs) if crc32 else outs
+
+    def rs_repair(self, payloads: list, dsize: int, codesize: int):
+        """ecc.decode(p, dsize, codesize, repair=True) of every payload (tools/ecc.py:14-25) on the device.
+        -> (data parts, corrected blocks per payload, failed blocks per payload)"""
+        t = self.torch
+        lib = self.core._lib.load()
+        n = len(payloads)
+        if n == 0:
+            return [], np.zeros(0, np.int32), np.zeros(0, np.int32)
+        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, True)
+        nout = int(out_off[-1])
+        out = t.empty(max((nout + 15) // 16 * 16, 16), dtype=t.uint8, device=self.device)
+        counts = t.empty(2 * n + n_blocks + 1, dtype=t.int32, device=self.device)    # corrected, failed, work list
+        stream = int(t.cuda.current_stream(self.device).cuda_stream)
+        with t.cuda.device(self.device):
+            lib.rs_repair(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), counts.data_ptr(), counts.data_ptr() + 4 * n,
+                          counts.data_ptr() + 8 * n, stream)
+        host = self._down_bytes(out[:nout]) if nout else b""
+        cnt = counts[:2 * n].cpu().numpy()
+        del dev
+        return [host[out_off[i]:out_off[i + 1]] for i in range(n)], cnt[:n].copy(), cnt[n:].copy()

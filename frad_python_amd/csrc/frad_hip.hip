@@ -266,6 +266,7 @@ void frad_plan_clear(void) {
     blue_clear();
     mixed_clear();
     crc_clear();
+    ecc_clear();
     p1_clear();
     wave_clear();
 }

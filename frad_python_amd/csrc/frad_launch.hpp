@@ -108,6 +108,7 @@ int global_p0_digital(const unsigned char* payload, double* out, const Geom& g, 
 int global_last_hip_error();
 // CRC-32 tables (frad_crc.hip)
 void crc_clear();
+void ecc_clear();        // Reed-Solomon tables (frad_ecc.hip)
 void p1_clear();         // profile-1 band maps (frad_p1.hip)
 int crc_last_hip_error();
 

@@ -10,7 +10,7 @@ import zlib
 
 import numpy as np
 
-from . import common
+from . import common, ecc
 from .fourier import profiles
 from .tools.asfh import ASFH
 from .backend.pcmformat import from_f64
@@ -48,15 +48,22 @@ def _strip_ecc(frad: bytes, dsize: int, codesize: int) -> bytes:
     return b"".join(frad[i:i + block][:max(len(frad[i:i + block]) - codesize, 0)] for i in range(0, len(frad), block))
 
 
+class _Damaged:
+    """An ECC payload whose checksum fails, waiting for the batched repair of its run (frad_rs_repair)."""
+    __slots__ = ("frad", "dsize", "codesize")
+
+    def __init__(self, frad: bytes, dsize: int, codesize: int):
+        self.frad, self.dsize, self.codesize = frad, dsize, codesize
+
+
 class Decoder:
     def __init__(self, fix_error: bool = False, *, bridge=None, out_format: str | None = None):
-        """``out_format`` (extension): a PCM format name; DecodeResult.pcm then holds ``from_f64(pcm, fmt).astype(fmt)``
+        """``fix_error``: ECC frames whose stored checksum does not match are repaired (Reed-Solomon, on the device) before
+        they are decoded; a block that cannot be corrected becomes zero bytes (decoder.py:63-68, tools/ecc.py:14-25).
+        ``out_format`` (extension): a PCM format name; DecodeResult.pcm then holds ``from_f64(pcm, fmt).astype(fmt)``
         -- what the reference's caller computes right after every process() (src/decoder.py:23) -- done on the device
         for the bulk path, so that 2-8 bytes per sample cross PCIe instead of 8."""
         self.out_format = out_format
-        if fix_error:
-            raise NotImplementedError("Reed-Solomon repair is host-side and needs the third-party reedsolo module; "
-                                      "it is outside the MI355X transform core")
         self.asfh = ASFH()
         self.info = ASFH()
         self.buffer = b""
@@ -90,6 +97,7 @@ class Decoder:
     def _decode_run_f64(self, key, entries: list) -> list:
         """entries: (payload bytes or None, offset in self._data, length) per frame of the run"""
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
+        entries = self._repair(entries)
         strided = getattr(self.bridge, "lossless_decode_strided", None)
         if (profile != 1 and strided is not None and len(entries) > 1 and all(e[0] is None for e in entries)):
             step = entries[1][1] - entries[0][1]
@@ -132,6 +140,31 @@ class Decoder:
         else:
             pcm = self.bridge.lossless_decode(profile, payloads, fsize, channels, _LOSSLESS_DEPTHS[depth_idx], endian)
         return self._finish_run(pcm, key)
+
+    def _repair(self, entries: list) -> list:
+        """Replace the run's damaged payloads by their repaired data parts: one frad_rs_repair batch per stored ratio."""
+        groups = {}
+        for i, e in enumerate(entries):
+            if isinstance(e[0], _Damaged):
+                groups.setdefault((e[0].dsize, e[0].codesize), []).append(i)
+        if not groups:
+            return entries
+        entries = list(entries)
+        for (dsize, csize), idx in groups.items():
+            if not 1 <= dsize + csize <= 255:
+                raise ValueError(f"Reed-Solomon blocks of {dsize} + {csize} bytes cannot be decoded")
+            fixed, _, _ = self.bridge.rs_repair([entries[i][0].frad for i in idx], dsize, csize)
+            for i, f in zip(idx, fixed):
+                entries[i] = (f, entries[i][1], entries[i][2])
+        return entries
+
+    def _unprotect(self, frad: bytes, profile: int, dsize: int, csize: int, crc: int):
+        """ecc.decode (decoder.py:63-68): strip the check bytes, or -- fix_error and a failing checksum -- mark the payload
+        for repair.  -> (payload or _Damaged, data bytes)"""
+        if self.fix_error and ecc.needs_repair(profile, frad, crc):
+            return _Damaged(frad, dsize, csize), ecc.data_len(len(frad), dsize, csize)
+        frad = _strip_ecc(frad, dsize, csize)
+        return frad, len(frad)
 
     def _finish_run(self, pcm: np.ndarray, key) -> list:
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
@@ -207,12 +240,12 @@ class Decoder:
             raise NotImplementedError(f"profile {a.profile} is not built (upstream: in development)")
         # lossless payloads stay where they are in the stream (offset, length): a run of equally spaced frames goes to
         # the device as one strided buffer; everything else is cut out here
-        frad = None
+        frad, nb = None, need
         if a.profile == 1 or a.ecc:
             frad = self._data[off:off + need]
+            nb = len(frad)
             if a.ecc:
-                frad = _strip_ecc(frad, a.ecc_dsize, a.ecc_codesize)
-        nb = need if frad is None else len(frad)
+                frad, nb = self._unprotect(frad, a.profile, a.ecc_dsize, a.ecc_codesize, int.from_bytes(a.crc, "big"))
         fsize = a.fsize if a.profile == 1 else _lossless_frame_len(nb, a.bit_depth_index, a.channels, a.fsize)
         key = (a.profile, fsize, a.channels, a.bit_depth_index, a.endian, a.srate, a.overlap_ratio)
         a.clear()
@@ -318,8 +351,8 @@ class Decoder:
         table, next_pos, why = self._scan(self._data, self._pos)
         a = self.asfh
         rows = table.tolist()
-        for (h_off, p_off, p_len, profile, ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc) in rows:
-            a.profile, a.ecc, a.endian, a.bit_depth_index = profile, bool(ecc), bool(le), depth
+        for (h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc) in rows:
+            a.profile, a.ecc, a.endian, a.bit_depth_index = profile, bool(is_ecc), bool(le), depth
             a.channels, a.srate, a.fsize, a.frmbytes = ch, srate, fsize, p_len
             if fflush:
                 self._pos = p_off
@@ -333,12 +366,12 @@ class Decoder:
                     return "crit"
             if profile not in (0, 1, 4):
                 raise NotImplementedError(f"profile {profile} is not built (upstream: in development)")
-            frad = None
-            if profile == 1 or ecc:
+            frad, nb = None, p_len
+            if profile == 1 or is_ecc:
                 frad = self._data[p_off:p_off + p_len]
-                if ecc:
-                    frad = _strip_ecc(frad, dsize, csize)
-            nb = p_len if frad is None else len(frad)
+                nb = len(frad)
+                if is_ecc:
+                    frad, nb = self._unprotect(frad, profile, dsize, csize, crc)
             n_eff = fsize if profile == 1 else _lossless_frame_len(nb, depth, ch, fsize)
             key = (profile, n_eff, ch, depth, bool(le), srate, ratio)
             append(key, (frad, p_off, nb))

@@ -242,9 +242,10 @@ class Encoder:
         self.bit_depth = bit_depth
 
     def set_ecc(self, ecc: bool, ecc_ratio):
+        # protected streams come from Repairer(ecc_ratio).process(stream), which writes the bytes set_ecc(True, ...) would
         if ecc:
-            raise NotImplementedError("Reed-Solomon ECC is host-side and not part of the MI355X transform core "
-                                      "(the reference needs the third-party reedsolo module for it)")
+            raise NotImplementedError("Encoder-side ECC is not built: protect the stream with "
+                                      "frad_python_amd.Repairer(ecc_ratio).process(stream), which writes the same bytes")
         self.asfh.ecc = False
         self.asfh.ecc_dsize, self.asfh.ecc_codesize = ecc_ratio if ecc_ratio[0] and sum(ecc_ratio) <= 255 else (96, 24)
 

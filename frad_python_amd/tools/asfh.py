@@ -10,7 +10,8 @@ fields), because Encoder/Decoder and their callers use it as the frame descripto
     compact profiles (1, 2), 12 bytes :  9 css(2) = (channels-1)<<10 | srate idx<<6 | fsize idx<<1 | flush
                                          | 11 overlap_ratio-1 | with ECC, 16 bytes: 12 dsize | 13 codesize | 14 crc16(2)
     length field 0xFFFFFFFF: a u64 length follows the header.
-Framing, CRC and Reed-Solomon stay on the host CPU by design (BASELINE.json north_star)."""
+Framing stays on the host (the decoder's bulk path uses the native scanner frad_asfh_scan); the CRC-32 of a batch and
+Reed-Solomon protection / repair (Repairer, Decoder(fix_error=True)) run on the device (frad_crc32_frames, frad_rs_*)."""
 from __future__ import annotations
 
 import struct

@@ -188,6 +188,28 @@ int frad_p1_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_
  * stream can be assembled without a host pass over the payload.                                   */
 int frad_crc32_frames(const void* data, int64_t stride, int64_t n_frames, int64_t nbytes, uint32_t* crc_out, void* stream);
 
+/* ---- Reed-Solomon frame protection (src/libfrad/tools/ecc.py: reedsolo.RSCodec(codesize, dsize + codesize), GF(2^8) over
+ * 0x11d, alpha = 2, first consecutive root 0) ------------------------------------------------------------------------------
+ * A batch is n_frames byte strings back to back: frame f is in[in_off[f] .. in_off[f+1]) and its output goes to
+ * out[out_off[f] .. out_off[f+1]); blk_off[f+1] - blk_off[f] is its block count, blk_off[0] = 0, n_blocks = blk_off[n_frames].
+ * in_off / blk_off / out_off are DEVICE int64 arrays of n_frames + 1 entries that the caller fills as below; `in` and `out`
+ * must be 16-byte aligned.
+ * frad_rs_encode == ecc.encode (ecc.py:6-12) of every frame: blocks of dsize bytes (the last may be shorter), each written
+ * as data || codesize check bytes.  blk_off[f+1] - blk_off[f] = ceil(len_f / dsize), out_len_f = len_f + blocks_f * codesize.
+ * 1 <= dsize, 0 <= codesize, dsize + codesize <= 255.
+ * frad_rs_repair == ecc.decode(..., repair=True) (ecc.py:14-25) of every frame: blocks of dsize + codesize stored bytes, each
+ * replaced by its data part (block length - codesize bytes, none when the block is not longer than codesize), corrected
+ * when a codeword lies within codesize / 2 byte errors of the block and zero-filled otherwise.  blocks_f =
+ * ceil(len_f / (dsize + codesize)), out_len_f = len_f - codesize * blocks_f + (codesize - len of a last block shorter than
+ * codesize, if any).  corrected[f] / failed[f] (device int32 [n_frames]) count frame f's blocks that needed a correction
+ * and got one / could not be corrected.  `work` is device int32 scratch of n_blocks + 1 entries.
+ * 0 <= dsize, 0 <= codesize, 1 <= dsize + codesize <= 255. */
+int frad_rs_encode(const void* in, const int64_t* in_off, const int64_t* blk_off, const int64_t* out_off, int64_t n_frames,
+                   int64_t n_blocks, int32_t dsize, int32_t codesize, void* out, void* stream);
+int frad_rs_repair(const void* in, const int64_t* in_off, const int64_t* blk_off, const int64_t* out_off, int64_t n_frames,
+                   int64_t n_blocks, int32_t dsize, int32_t codesize, void* out, int32_t* corrected, int32_t* failed,
+                   int32_t* work, void* stream);
+
 /* ---- decoder output conversion (R1 epilogue) and native frame-header scan (row 8f #1) ------------------------------
  * frad_from_f64 == backend.pcmformat.from_f64 followed by .astype(fmt) as the reference's caller applies it to every
  * decoded block (backend/pcmformat.py:49-62, src/decoder.py:23): float64 [n_values] -> `out_dtype` (FRAD_PCM_*), floats
