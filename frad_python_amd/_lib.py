@@ -47,6 +47,8 @@ SYMBOLS = {
     "frad_p1_golomb_encode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "frad_rows_compact": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "frad_p1_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p2_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p2_synth": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "frad_from_f64": (c_int, [c_void_p, c_int64, c_int32, c_uint32, c_void_p, c_void_p]),
     "frad_p0_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
     "frad_p4_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
@@ -162,6 +164,12 @@ class FradLib:
 
     def p1_golomb_decode(self, bodies, offsets, n_frames, N, C, q, tq, status, stream=0):
         self._check(self.dll.frad_p1_golomb_decode(bodies, offsets, n_frames, N, C, q, tq, status, stream))
+
+    def p2_golomb_decode(self, bodies, offsets, n_frames, N, C, q, tq, lpc, status, stream=0):
+        self._check(self.dll.frad_p2_golomb_decode(bodies, offsets, n_frames, N, C, q, tq, lpc, status, stream))
+
+    def p2_synth(self, q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream=0):
+        self._check(self.dll.frad_p2_synth(q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream))
 
     def from_f64(self, pcm, n_values, out_dtype, out, stream=0, flags=FRAD_RAW_BE_INTS):
         self._check(self.dll.frad_from_f64(pcm, n_values, out_dtype, flags, out, stream))

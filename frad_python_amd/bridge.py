@@ -162,6 +162,34 @@ class HipBridge:
             pcm = out.cpu().numpy().reshape(-1, C)
         return pcm, nxt.cpu().numpy()
 
+    def _p2_integers(self, bodies: list, N, C):
+        t = self.torch
+        off = np.zeros(len(bodies) + 1, np.int64)
+        np.cumsum([len(b) for b in bodies], out=off[1:])
+        flat = self._up(b"".join(bodies) + bytes(8))              # aligned 32-bit word reads: tail slack (frad_hip.h)
+        return self.core.p2_golomb_decode_batch(flat, t.from_numpy(off).to(self.device), N, C)
+
+    def p2_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
+        """Inflated profile-2 bodies -> PCM [n_frames, N, C] (profile2.py:64-91): Golomb decode, TNS synthesis and the
+        threshold ramp (frad_p2_synth), inverse DCT (frad_p0_digital); one upload of the bodies, one download."""
+        q, tq, lpc, _ = self._p2_integers(bodies, N, C)
+        return self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate).cpu().numpy()
+
+    def p2_decode_run(self, bodies: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
+        """``p1_decode_run`` for profile 2: the run of overlapped frames whole on the device, through the cross-fade and
+        the optional output conversion.  -> (PCM [n_frames * cut, C], new tail float64)"""
+        from .backend.pcmformat import ff_format_to_numpy_type
+        t = self.torch
+        q, tq, lpc, _ = self._p2_integers(bodies, N, C)
+        frames = self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate)
+        pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
+        out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
+        if out.dtype == t.uint8:
+            pcm = np.frombuffer(out.cpu().numpy().tobytes(), ff_format_to_numpy_type(out_format)).reshape(-1, C)
+        else:
+            pcm = out.cpu().numpy().reshape(-1, C)
+        return pcm, nxt.cpu().numpy()
+
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch
         return self.core.p1_digital_batch(t.from_numpy(np.ascontiguousarray(q, np.int32)).to(self.device),

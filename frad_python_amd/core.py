@@ -346,6 +346,59 @@ def p1_digital_batch(q: torch.Tensor, tq: torch.Tensor, N: int, C: int, bits: in
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# profile 2 (TNS): decode only (the reference's encoder refuses profile 2, fourier/__init__.py AVAILABLE)
+# ---------------------------------------------------------------------------------------------
+P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)                # ref: fourier/profile2.py:7
+P2_LPC = 13                                            # MAX_ORDER + 1 integers per channel (tools/p2tools.py:4)
+
+
+def _require_int32(t: torch.Tensor, shape: tuple, what: str):
+    if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 tensor of shape {list(shape)} (got {t.dtype} {list(t.shape)})")
+
+
+def p2_golomb_decode_batch(bodies: torch.Tensor, offsets: torch.Tensor, N: int, C: int):
+    """The three ``exp_golomb_rice_decode`` calls + ``untrim`` of ``profile2.digital`` (profile2.py:64-76): inflated bodies
+    (uint8, frame i at ``offsets[i]:offsets[i+1]``, 8 readable bytes after the last) -> ``(q [n, N, C], tq [n, 27, C],
+    lpc [n, 13, C], status [n])``; status 1 = the body's prefix does not fit (decoded as a frame of zeros)."""
+    _require_cuda(bodies, "bodies"); _require_cuda(offsets, "offsets")
+    if bodies.dtype != torch.uint8 or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("bodies must be uint8 and offsets a 1-D int64 tensor of n_frames + 1 entries")
+    n_frames = offsets.numel() - 1
+    q = torch.empty((n_frames, N, C), dtype=torch.int32, device=bodies.device)
+    tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=bodies.device)
+    lpc = torch.empty((n_frames, P2_LPC, C), dtype=torch.int32, device=bodies.device)
+    status = torch.empty(max(n_frames, 1), dtype=torch.int32, device=bodies.device)
+    with torch.cuda.device(bodies.device):
+        _lib.load().p2_golomb_decode(bodies.data_ptr(), offsets.data_ptr(), n_frames, N, C, q.data_ptr(), tq.data_ptr(),
+                                     lpc.data_ptr(), status.data_ptr(), _stream_ptr())
+    return q, tq, lpc, status[:n_frames]
+
+
+def p2_synth_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor, N: int, C: int, bits: int, srate: int) -> torch.Tensor:
+    """Dequantisation, TNS synthesis and the threshold ramp of ``profile2.digital`` (profile2.py:69-86): float64 coefficients
+    [n_frames, N, C], i.e. a 64-bit little-endian profile-0 payload (``p2_digital_batch`` finishes the frame)."""
+    _require_cuda(q, "q"); _require_cuda(tq, "tq"); _require_cuda(lpc, "lpc")
+    if bits not in P2_DEPTHS:
+        raise ValueError(f"profile 2 depth must be one of {P2_DEPTHS}, got {bits}")
+    n_frames = q.shape[0] if q.dim() == 3 else -1
+    _require_int32(q, (n_frames, N, C), "q")
+    _require_int32(tq, (n_frames, P1_BANDS, C), "tq")
+    _require_int32(lpc, (n_frames, P2_LPC, C), "lpc")
+    out = torch.empty((n_frames, N, C), dtype=torch.float64, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.load().p2_synth(q.data_ptr(), tq.data_ptr(), lpc.data_ptr(), n_frames, N, C, bits, srate, out.data_ptr(), _stream_ptr())
+    return out
+
+
+def p2_digital_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor, N: int, C: int, bits: int, srate: int) -> torch.Tensor:
+    """``profile2.digital`` from the decoded integers on: ``p2_synth_batch`` then the inverse DCT of the coefficient plane
+    (frad_p0_digital at 64-bit little-endian storage, every compact size) -> float64 PCM [n_frames, N, C]."""
+    coeffs = p2_synth_batch(q, tq, lpc, N, C, bits, srate)
+    return digital_batch(0, coeffs.view(torch.uint8).reshape(coeffs.shape[0], -1), coeffs.shape[0], N, C, 64, True)
+
+
 def p1_overlap_add(frames: torch.Tensor, overlap_ratio: int, prev_tail: torch.Tensor | None = None, out_format: str | None = None):
     """The decoder's Hann cross-fade over consecutive decoded frames (decoder.py:28-46).
 

@@ -387,11 +387,13 @@ __device__ __forceinline__ void decode_stream_wave(const unsigned char* p, long 
 
 __global__ void __launch_bounds__(64) k_gol_decode(const unsigned char* __restrict__ bodies, const long long* __restrict__ offsets, long long n_frames,
                                                    long long nq, long long ntq, int32_t* __restrict__ q, int32_t* __restrict__ tq,
-                                                   int32_t* __restrict__ status, const int32_t* __restrict__ todo) {
+                                                   int32_t* __restrict__ status, const int32_t* __restrict__ todo,
+                                                   const long long* __restrict__ starts) {
     const long long f = (long long)blockIdx.x * 64 + threadIdx.x;
     const bool live = f < n_frames;                           // spare lanes of the last wave keep the rounds uniform
-    const unsigned char* b = live ? bodies + offsets[f] : bodies;
-    long long len = live ? offsets[f + 1] - offsets[f] : 0;
+    const long long s0 = live ? (starts ? starts[f] : offsets[f]) : 0;      // starts: profile 2, past the LPC part (k_p2_prefix)
+    const unsigned char* b = live ? bodies + s0 : bodies;
+    long long len = live ? offsets[f + 1] - s0 : 0;
     long long tlen = 0;
     const int mine = live ? (todo ? todo[f] : 3) : 0;         // streams the wave-per-frame kernel left to this one (bit 0: tq, bit 1: q)
     if (live && status && !todo) status[f] = len < 4 ? 1 : 0;          // no length word: nothing decodable (the host treats it as broken)
@@ -698,12 +700,14 @@ __device__ __forceinline__ bool decode_stream_2phase(const unsigned char* p, lon
 template <bool MAP>
 __global__ void __launch_bounds__(64) k_gol_decode_wave(const unsigned char* __restrict__ bodies, const long long* __restrict__ offsets,
                                                         long long nq, long long ntq, int32_t* __restrict__ q, int32_t* __restrict__ tq,
-                                                        int32_t* __restrict__ status, int32_t* __restrict__ todo, int wmax, int omax) {
+                                                        int32_t* __restrict__ status, int32_t* __restrict__ todo, int wmax, int omax,
+                                                        const long long* __restrict__ starts) {
     const long long f = blockIdx.x;
     int mine = 3;
     if constexpr (MAP) { mine = todo[f]; if (mine == 0) return; }                  // (uniform: one wave, one frame)
-    const unsigned char* b = bodies + offsets[f];
-    long long len = offsets[f + 1] - offsets[f];
+    const long long s0 = starts ? starts[f] : offsets[f];
+    const unsigned char* b = bodies + s0;
+    long long len = offsets[f + 1] - s0;
     long long tlen = 0;
     if (!MAP && threadIdx.x == 0 && status) status[f] = len < 4 ? 1 : 0;
     if (len >= 4) {
@@ -715,6 +719,23 @@ __global__ void __launch_bounds__(64) k_gol_decode_wave(const unsigned char* __r
     if (threadIdx.x == 0) todo[f] = (ok_t ? 0 : 1) | (ok_q ? 0 : 2);
 }
 
+// profile 2 (profile2.py:63-67): '>H' lpc_len | lpc_gol | the profile-1 body.  One lane per frame decodes the LPC stream
+// (13 C values, cut and zero-filled) with the lane-per-frame parser and notes where the profile-1 part begins.  A body too
+// short for the prefix, or whose lpc_len leaves no room for the '>I' word (the reference raises on it), is marked broken:
+// starts[f] = its end, so the profile-1 kernels see an empty body (status 1, zero fill).
+__global__ void __launch_bounds__(64) k_p2_prefix(const unsigned char* __restrict__ bodies, const long long* __restrict__ offsets,
+                                                  long long n_frames, long long nlpc, int32_t* __restrict__ lpc,
+                                                  long long* __restrict__ starts) {
+    const long long f = (long long)blockIdx.x * 64 + threadIdx.x;
+    const bool live = f < n_frames;
+    const unsigned char* b = live ? bodies + offsets[f] : bodies;
+    const long long len = live ? offsets[f + 1] - offsets[f] : 0;
+    const long long llen = len >= 2 ? ((long long)b[0] << 8) | (long long)b[1] : 0;
+    const bool ok = len >= 2 && 2 + llen + 4 <= len;
+    if (live) starts[f] = ok ? offsets[f] + 2 + llen : offsets[f + 1];
+    decode_stream_wave(b + 2, ok ? llen : 0, lpc + (live ? f * nlpc : 0), live ? nlpc : 0);
+}
+
 thread_local int g_gol_hip = 0;
 #define GOLCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_gol_hip = (int)e_; return FRAD_E_HIP; } } while (0)
 
@@ -723,6 +744,39 @@ int golomb_last_hip_error() { return g_gol_hip; }
 }  // namespace frad
 
 using namespace frad;
+
+namespace {
+// the profile-1 streams of frame i start at starts[i] (NULL: offsets[i]) and end at offsets[i + 1]
+int gol_decode(const void* bodies, const int64_t* offsets, const long long* starts, int64_t n_frames, int32_t N, int32_t C,
+               int32_t* q, int32_t* tq, int32_t* status, hipStream_t s) {
+    const long long blocks = ((long long)n_frames + 63) / 64;
+    static const bool no_wave = [] { const char* e = std::getenv("FRAD_TUNE_GOLOMB_LANE"); return e && e[0] == '1'; }();
+    int32_t* todo = nullptr;
+    if (!no_wave) {
+        // fast path: one wave per frame; what it cannot take (codes > 64 bits, k > 30, streams beyond its LDS) is marked in
+        // `todo` and decoded by the lane-per-frame kernel behind it
+        if (hipMallocAsync(reinterpret_cast<void**>(&todo), sizeof(int32_t) * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+        // LDS budget: 16 bits per coefficient on average (a frame above that goes to the slow kernel): at N C = 4096 that is
+        // 8.4 KiB of stream per wave
+        long long wmax = ((long long)N * C * 16) / 32 + 64;
+        if (wmax > GW_WORDS) wmax = GW_WORDS;
+        // + a short stream's values on their way out (the thresholds; a frame of <= 512 coefficients).  Staging whole frames of
+        // 4096 was measured: 25 KiB per wave leaves six waves on a CU -- 0.46 ms per 15 000 frames against 0.37 without
+        const long long nq = (long long)N * C, nst = nq <= 512 ? nq : 27LL * C;
+        const int omax = (int)(nst + (nst >> 5) + 1);
+        hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax), s, static_cast<const unsigned char*>(bodies),
+                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax, starts);
+        // behind it, for the streams the walks did not settle (a wave whose frame has none returns at once): the entry maps
+        hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax, true), s, static_cast<const unsigned char*>(bodies),
+                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax, starts);
+    }
+    hipLaunchKernelGGL(k_gol_decode, dim3((unsigned)blocks), dim3(64), DEC_LDS, s, static_cast<const unsigned char*>(bodies),
+                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, (long long)N * C, 27LL * C, q, tq, status, todo, starts);
+    if (todo) (void)hipFreeAsync(todo, s);
+    GOLCHK(hipGetLastError());
+    return FRAD_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -771,11 +825,11 @@ int frad_debug_golomb_decode_wave(const void* bodies, const int64_t* offsets, in
     const int omax = (int)(nst + (nst >> 5) + 1);
     hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax), static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char*>(bodies), reinterpret_cast<const long long*>(offsets), nq, 27LL * C, q, tq,
-                       static_cast<int32_t*>(nullptr), todo, (int)wmax, omax);
+                       static_cast<int32_t*>(nullptr), todo, (int)wmax, omax, static_cast<const long long*>(nullptr));
     if (with_maps)
         hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax, true), static_cast<hipStream_t>(stream),
                            static_cast<const unsigned char*>(bodies), reinterpret_cast<const long long*>(offsets), nq, 27LL * C, q, tq,
-                           static_cast<int32_t*>(nullptr), todo, (int)wmax, omax);
+                           static_cast<int32_t*>(nullptr), todo, (int)wmax, omax, static_cast<const long long*>(nullptr));
     GOLCHK(hipGetLastError());
     return FRAD_OK;
 }
@@ -785,34 +839,24 @@ int frad_p1_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_
     if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!bodies || !offsets || !q || !tq) return FRAD_E_INVALID;
-    const long long blocks = ((long long)n_frames + 63) / 64;
+    if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
+    return gol_decode(bodies, offsets, nullptr, n_frames, N, C, q, tq, status, static_cast<hipStream_t>(stream));
+}
+
+int frad_p2_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_frames, int32_t N, int32_t C,
+                          int32_t* q, int32_t* tq, int32_t* lpc, int32_t* status, void* stream) {
+    if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
+    if (n_frames == 0) return FRAD_OK;
+    if (!bodies || !offsets || !q || !tq || !lpc) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static const bool no_wave = [] { const char* e = std::getenv("FRAD_TUNE_GOLOMB_LANE"); return e && e[0] == '1'; }();
-    int32_t* todo = nullptr;
-    if (!no_wave) {
-        // fast path: one wave per frame; what it cannot take (codes > 64 bits, k > 30, streams beyond its LDS) is marked in
-        // `todo` and decoded by the lane-per-frame kernel behind it
-        if (hipMallocAsync(reinterpret_cast<void**>(&todo), sizeof(int32_t) * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
-        // LDS budget: 16 bits per coefficient on average (a frame above that goes to the slow kernel): at N C = 4096 that is
-        // 8.4 KiB of stream per wave
-        long long wmax = ((long long)N * C * 16) / 32 + 64;
-        if (wmax > GW_WORDS) wmax = GW_WORDS;
-        // + a short stream's values on their way out (the thresholds; a frame of <= 512 coefficients).  Staging whole frames of
-        // 4096 was measured: 25 KiB per wave leaves six waves on a CU -- 0.46 ms per 15 000 frames against 0.37 without
-        const long long nq = (long long)N * C, nst = nq <= 512 ? nq : 27LL * C;
-        const int omax = (int)(nst + (nst >> 5) + 1);
-        hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax), s, static_cast<const unsigned char*>(bodies),
-                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax);
-        // behind it, for the streams the walks did not settle (a wave whose frame has none returns at once): the entry maps
-        hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax, true), s, static_cast<const unsigned char*>(bodies),
-                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax);
-    }
-    hipLaunchKernelGGL(k_gol_decode, dim3((unsigned)blocks), dim3(64), DEC_LDS, s, static_cast<const unsigned char*>(bodies),
-                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, (long long)N * C, 27LL * C, q, tq, status, todo);
-    if (todo) (void)hipFreeAsync(todo, s);
-    GOLCHK(hipGetLastError());
-    return FRAD_OK;
+    long long* starts = nullptr;
+    if (hipMallocAsync(reinterpret_cast<void**>(&starts), sizeof(long long) * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+    hipLaunchKernelGGL(k_p2_prefix, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), DEC_LDS, s, static_cast<const unsigned char*>(bodies),
+                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, 13LL * C, lpc, starts);
+    const int rc = gol_decode(bodies, offsets, starts, n_frames, N, C, q, tq, status, s);
+    (void)hipFreeAsync(starts, s);
+    return rc;
 }
 
 }  // extern "C"

@@ -306,6 +306,28 @@ int frad_p1_digital(const int32_t* q, const int32_t* tq, int64_t n_frames, int32
     return p1_digital_out(q, tq, n_frames, N, C, bits, srate, FRAD_PCM_F64LE, 0, pcm_out, stream);
 }
 
+int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
+                  int32_t srate, double* coeffs_out, void* stream) {
+    if (n_frames < 0 || C < 1 || C > 64 || !legal_compact_size(N)) return FRAD_E_INVALID;
+    bool depth = false;
+    for (int b : {8, 10, 12, 14, 16, 20, 24}) depth |= b == bits;       // profile2.py:7 DEPTHS (not profile 1's table)
+    if (!depth) return FRAD_E_INVALID;
+    if (n_frames == 0) return FRAD_OK;
+    if (!q || !tq || !lpc || !coeffs_out) return FRAD_E_INVALID;
+    if (n_frames > 0x7fffffffLL * 64 / C) return FRAD_E_UNSUPPORTED;
+    P1Tables tb;
+    const int rc = make_tables(N, srate, 16, 1.0, tb);
+    if (rc != FRAD_OK) return rc;
+    P1Edges pe;
+    for (int i = 0; i <= P1_BANDS; ++i) pe.edge[i] = tb.edge[i] < N ? tb.edge[i] : N;
+    const size_t lds = (size_t)((N + 15) / 16) * 16 + 32 * 4;              // the band map and the clipped edges
+    const long long blocks = (n_frames * C + 63) / 64;
+    hipLaunchKernelGGL(k_p2_synth<0>, dim3((unsigned)blocks), dim3(64), lds, static_cast<hipStream_t>(stream), q, tq, lpc, coeffs_out,
+                       (long long)n_frames, N, C, ldexp(1.0, bits - 1), tb.band_of, pe);
+    P1CHK(hipGetLastError());
+    return FRAD_OK;
+}
+
 }  // extern "C"
 namespace frad {
 // frad_p1_digital, optionally with the decoder's output conversion applied by the kernel's own store (frad_p1_digital_pcm):

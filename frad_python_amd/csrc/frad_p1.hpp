@@ -28,6 +28,9 @@ struct P1Tables {
                                  // and band energies are float32 and only the divide + quantiser are float64
 };
 
+// band edges clipped to N, by value (profile 2's kernel copies them to LDS)
+struct P1Edges { int edge[P1_BANDS + 1]; };
+
 // frad_global.hip: profile 1 through HBM workspaces (frames wider than a CU's LDS at a non-power-of-two size)
 int global_p1_analogue(const unsigned char* pcm, int32_t* q, int32_t* tq, const Geom& g, const P1Tables& tb, hipStream_t s);
 int global_p1_digital(const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb, hipStream_t s);
@@ -91,15 +94,18 @@ __device__ __forceinline__ void p1_ramp_steps(const P1Lds& l, int cfs) {
         l.step[i] = st;
     }
 }
+// bin i of a band of `num` bins from t0 towards t1, st = (t1 - t0) / num
+__device__ __forceinline__ double p1_ramp(double i, int num, double st, double t0, double t1) {
+    double y = i * st;
+    if (st == 0.0) y = (i / (double)num) * (t1 - t0);                                 // numpy's denormal-safe branch
+    return y + t0;
+}
 __device__ __forceinline__ double p1_spread(const P1Lds& l, int cf, int k) {
     const int j = l.band[k];
     if (j >= P1_BANDS - 1) return 0.0;
     const double* thres = l.thres + cf * P1_BANDS;
     const int a = l.edge[j];
-    const double i = (double)(k - a), st = l.step[cf * P1_BANDS + j];
-    double y = i * st;
-    if (st == 0.0) y = (i / (double)(l.edge[j + 1] - a)) * (thres[j + 1] - thres[j]);    // numpy's denormal-safe branch
-    return y + thres[j];
+    return p1_ramp((double)(k - a), l.edge[j + 1] - a, l.step[cf * P1_BANDS + j], thres[j], thres[j + 1]);
 }
 
 // K7 epilogue: X[k] of `nfl` frames x `cw` channels sit in LDS (xslot<double, SH>); the channels are c0 .. c0+cw-1 of
@@ -343,6 +349,86 @@ __global__ void __launch_bounds__(256) k_p1_inv_direct(const int32_t* __restrict
     }
     __syncthreads();
     store_pcm_f64<-1, false>(N * C * 8, out, g, f0, 1, N);
+}
+
+// profile 2 (fourier/profile2.py:69-86, tools/p2tools.py:105-115): dequantise, TNS synthesis, threshold ramp -> the
+// coefficient plane [n_frames, N, C] (float64), which frad_p0_digital then inverts as a 64-bit little-endian payload.
+// The synthesis filter 1 / A(z) runs along the bins, a serial recursion per (frame, channel): one lane per channel, 64
+// consecutive (frame, channel) pairs per wave, all lanes at the same bin (the band changes are uniform).  The state is
+// direct form II transposed in scipy.signal.lfilter's order (y = z0 + x; z_k = z_{k+1} - a_{k+1} y; b = [1]), so every
+// rounding is the reference's.  The fallback (a NaN, an Inf or |y| > 1e6 anywhere in the channel -> the unfiltered
+// coefficients) is decided as the filter runs; the rare channel that trips it is rewritten in a second pass.  N is a
+// multiple of 32 (compact sizes), so every lane reads its bins P2_CHUNK at a time, those loads in flight together (staging the
+// chunks through LDS for coalesced rows was measured slower: DESIGN.md section 4d).
+constexpr int P2_ORDER = 12;
+constexpr int P2_CHUNK = 16;
+__device__ __forceinline__ double p2_thres(const int32_t* __restrict__ tq, long long row, int C, int b) {
+    return pow(2.718281828459045 / 2, p1_quant((double)tq[row + (long long)b * C]));
+}
+template <int UNUSED>
+__global__ void __launch_bounds__(64) k_p2_synth(const int32_t* __restrict__ q, const int32_t* __restrict__ tq, const int32_t* __restrict__ lpc,
+                                                 double* __restrict__ out, long long n_frames, int N, int C, double scale,
+                                                 const unsigned char* __restrict__ band_of, P1Edges pe) {
+    FRAD_DYN_SMEM(smem);
+    unsigned char* band = smem;
+    int* edge = reinterpret_cast<int*>(smem + ((N + 15) / 16) * 16);
+    for (int i = threadIdx.x; i < N / 4; i += blockDim.x) reinterpret_cast<uint32_t*>(band)[i] = reinterpret_cast<const uint32_t*>(band_of)[i];
+    if (threadIdx.x <= P1_BANDS) edge[threadIdx.x] = pe.edge[threadIdx.x];
+    __syncthreads();
+    const long long g = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_frames * C) return;
+    const long long f = g / C;
+    const int c = (int)(g - f * C);
+    const int32_t* qc = q + f * (long long)N * C + c;
+    double* oc = out + f * (long long)N * C + c;
+    const long long trow = f * (long long)(P1_BANDS * C) + c;
+    double a[P2_ORDER];
+    bool filt = false;
+    {
+        const int32_t* lc = lpc + f * (long long)((P2_ORDER + 1) * C) + c;
+        filt = lc[0] != 0;                                   // index 0 only decides "all zero" (dequantise_lpc)
+#pragma unroll
+        for (int i = 0; i < P2_ORDER; ++i) { const int32_t v = lc[(long long)(i + 1) * C]; filt |= v != 0; a[i] = (double)v / 15.0; }
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        double z[P2_ORDER];
+#pragma unroll
+        for (int i = 0; i < P2_ORDER; ++i) z[i] = 0.0;
+        bool bad = false;
+        int cj = -1, ca = 0, cnum = 1;
+        double t0 = 0.0, t1 = 0.0, st = 0.0;
+        for (int k0 = 0; k0 < N; k0 += P2_CHUNK) {
+            int32_t qv[P2_CHUNK];
+#pragma unroll
+            for (int u = 0; u < P2_CHUNK; ++u) qv[u] = qc[(long long)(k0 + u) * C];
+#pragma unroll
+            for (int u = 0; u < P2_CHUNK; ++u) {
+                const int k = k0 + u;
+                const double x = p1_dequant((double)qv[u]) / scale;
+                double y = x;
+                if (filt) {
+                    y = z[0] + x;
+#pragma unroll
+                    for (int i = 0; i < P2_ORDER - 1; ++i) z[i] = z[i + 1] - y * a[i];
+                    z[P2_ORDER - 1] = 0.0 - y * a[P2_ORDER - 1];
+                    bad |= !(fabs(y) <= 1e6);
+                }
+                const int j = band[k];                       // the same bin in every lane: uniform
+                if (j != cj) {
+                    cj = j;
+                    if (j < P1_BANDS - 1) {
+                        ca = edge[j]; cnum = edge[j + 1] - ca;
+                        t0 = p2_thres(tq, trow, C, j); t1 = p2_thres(tq, trow, C, j + 1);
+                        st = cnum > 0 ? (t1 - t0) / (double)cnum : 0.0;
+                    }
+                }
+                const double r = j < P1_BANDS - 1 ? p1_ramp((double)(k - ca), cnum, st, t0, t1) : 0.0;
+                oc[(long long)k * C] = y * r;
+            }
+        }
+        if (!(filt && bad)) break;
+        filt = false;                                        // the fallback: the same channel, unfiltered
+    }
 }
 
 // R8: decoder overlap-add over a batch of consecutive frames (decoder.py:28-46).  Frame i keeps

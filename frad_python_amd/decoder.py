@@ -17,6 +17,9 @@ from .backend.pcmformat import from_f64
 
 _LOSSLESS_DEPTHS = (12, 16, 24, 32, 48, 64)
 _P1_DEPTHS = (8, 12, 16, 24, 32, 48, 64)
+_P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)                 # fourier/profile2.py:7
+_DEFLATED = (1, 2)                                      # compact profiles: deflated Golomb bodies, cut from the stream
+_BUILT = (0, 1, 2, 4)
 
 
 class DecodeResult:
@@ -99,7 +102,7 @@ class Decoder:
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
         entries = self._repair(entries)
         strided = getattr(self.bridge, "lossless_decode_strided", None)
-        if (profile != 1 and strided is not None and len(entries) > 1 and all(e[0] is None for e in entries)):
+        if (profile not in _DEFLATED and strided is not None and len(entries) > 1 and all(e[0] is None for e in entries)):
             step = entries[1][1] - entries[0][1]
             if step > 0 and all(entries[i + 1][1] - entries[i][1] == step for i in range(len(entries) - 1)):
                 first, nb = entries[0][1], entries[0][2]
@@ -114,19 +117,20 @@ class Decoder:
                         return self._overlap_host(pcm, key)
                     return [pcm.reshape(-1, channels)]             # one piece: no per-frame list, no concatenate
         payloads = [e[0] if e[0] is not None else self._data[e[1]:e[1] + e[2]] for e in entries]
-        if profile == 1:
-            bits = _P1_DEPTHS[depth_idx]
-            # inflate on the host (profile1.py:59); Golomb decode + dequantise + IDCT behind the bridge (on the device)
+        if profile in _DEFLATED:
+            bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth_idx]
+            # inflate on the host (profile1.py:59, profile2.py:61); Golomb decode + dequantise (+ TNS) + IDCT behind the bridge
+            # (on the device)
             def inflate(frad):
                 try:
                     return zlib.decompress(frad, wbits=-15)
                 except Exception:
-                    return None                                      # profile1.py:59-60 -> a frame of zeros
+                    return None                                      # profile1.py:59-60, profile2.py:63-64 -> a frame of zeros
             from .encoder import _map_zlib
             bodies = _map_zlib(inflate, payloads)                  # runs of frames per pool task
             bad = [i for i, b in enumerate(bodies) if b is None]
             bodies = [b if b is not None else b"" for b in bodies]
-            fused = getattr(self.bridge, "p1_decode_run", None)
+            fused = getattr(self.bridge, "p1_decode_run" if profile == 1 else "p2_decode_run", None)
             L = fsize - fsize * (ratio - 1) // ratio if ratio else 0
             if fused is not None and ratio != 0 and (not self.overlap_fragment.size or self.overlap_fragment.shape == (L, channels)):
                 # the whole run on the device: Golomb decode, K8, the cross-fade and the output conversion; an undecodable frame
@@ -134,7 +138,7 @@ class Decoder:
                 prev = self.overlap_fragment if self.overlap_fragment.size else None
                 pcm, self.overlap_fragment = fused(bodies, fsize, channels, bits, srate, ratio, prev, self.out_format)
                 return [pcm]
-            pcm = self.bridge.p1_decode_bodies(bodies, fsize, channels, bits, srate)
+            pcm = (self.bridge.p1_decode_bodies if profile == 1 else self.bridge.p2_decode_bodies)(bodies, fsize, channels, bits, srate)
             for i in bad:
                 pcm[i] = 0.0
         else:
@@ -236,17 +240,17 @@ class Decoder:
         off = self._pos
         self._pos += need
         a = self.asfh
-        if a.profile not in (0, 1, 4):
+        if a.profile not in _BUILT:
             raise NotImplementedError(f"profile {a.profile} is not built (upstream: in development)")
         # lossless payloads stay where they are in the stream (offset, length): a run of equally spaced frames goes to
         # the device as one strided buffer; everything else is cut out here
         frad, nb = None, need
-        if a.profile == 1 or a.ecc:
+        if a.profile in _DEFLATED or a.ecc:
             frad = self._data[off:off + need]
             nb = len(frad)
             if a.ecc:
                 frad, nb = self._unprotect(frad, a.profile, a.ecc_dsize, a.ecc_codesize, int.from_bytes(a.crc, "big"))
-        fsize = a.fsize if a.profile == 1 else _lossless_frame_len(nb, a.bit_depth_index, a.channels, a.fsize)
+        fsize = a.fsize if a.profile in _DEFLATED else _lossless_frame_len(nb, a.bit_depth_index, a.channels, a.fsize)
         key = (a.profile, fsize, a.channels, a.bit_depth_index, a.endian, a.srate, a.overlap_ratio)
         a.clear()
         return key, (frad, off, nb)
@@ -284,7 +288,7 @@ class Decoder:
                 if got is None:
                     break
                 key, frad = got
-                if key != run_key or (key[0] != 1 and run and frad[2] != run[0][2]):
+                if key != run_key or (key[0] not in _DEFLATED and run and frad[2] != run[0][2]):
                     close_run()
                     run_key = key
                 run.append(frad)
@@ -335,7 +339,7 @@ class Decoder:
         return lib.asfh_scan if lib is not None else None
 
     def _append(self, key, entry):
-        if key != self._run_key or (key[0] != 1 and self._run and entry[2] != self._run[0][2]):
+        if key != self._run_key or (key[0] not in _DEFLATED and self._run and entry[2] != self._run[0][2]):
             if self._run:
                 self._pieces.extend(self._decode_run(self._run_key, self._run))
             self._run_key, self._run = key, []
@@ -364,15 +368,15 @@ class Decoder:
                 if any(previous):
                     self._pos, self._crit_srate = p_off, previous[0]
                     return "crit"
-            if profile not in (0, 1, 4):
+            if profile not in _BUILT:
                 raise NotImplementedError(f"profile {profile} is not built (upstream: in development)")
             frad, nb = None, p_len
-            if profile == 1 or is_ecc:
+            if profile in _DEFLATED or is_ecc:
                 frad = self._data[p_off:p_off + p_len]
                 nb = len(frad)
                 if is_ecc:
                     frad, nb = self._unprotect(frad, profile, dsize, csize, crc)
-            n_eff = fsize if profile == 1 else _lossless_frame_len(nb, depth, ch, fsize)
+            n_eff = fsize if profile in _DEFLATED else _lossless_frame_len(nb, depth, ch, fsize)
             key = (profile, n_eff, ch, depth, bool(le), srate, ratio)
             append(key, (frad, p_off, nb))
             self._scanned_frames += 1

@@ -182,6 +182,29 @@ int frad_rows_compact(const void* rows, int64_t row_stride, const int64_t* row_b
 int frad_p1_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_frames, int32_t N, int32_t C,
                           int32_t* q, int32_t* tq, int32_t* status, void* stream);
 
+/* ---- profile 2 (TNS) decode: fourier/profile2.py:58-91, tools/p2tools.py ------------------------------------------------
+ * frad_p2_golomb_decode == the three exp_golomb_rice_decode calls + untrim of profile2.digital (profile2.py:64-76): frame
+ * i's inflated body bodies[offsets[i] .. offsets[i+1]) is '>H' lpc_len | lpc_gol | '>I' thres_len | thres_gol | freqs_gol.
+ * lpc [n_frames, 13, C] receives the LPC integers (cut at 13*C, zero-filled), q / tq what frad_p1_golomb_decode writes
+ * for the rest of the body.  Same buffer rules (8 bytes of slack after the last body).
+ * Deviation on damaged streams only: a body too short for its '>H' word, or whose lpc_len leaves no room for the '>I'
+ * word, makes the reference raise (struct.error); here status[i] = 1 and all three arrays of that frame are zero-filled
+ * (a frame of zeros).  The profile-1 deviation above (missing band codes zero-filled as integers) applies as well.
+ *
+ * frad_p2_synth == profile2.digital's dequantisation (profile2.py:69-86): per frame and channel the coefficients
+ * dequant(q) / 2^(bits-1), filtered by tns_synthesis (p2tools.py:105-115: scipy.signal.lfilter([1], [1, lpc[1:]/15]),
+ * skipped when all 13 integers are 0, discarded when a result is NaN / Inf or above 1e6 in magnitude), times
+ * mapping_from_opus of the thresholds (e/2)^quant(tq) -- written as float64 coeffs_out [n_frames, N, C].  That plane is
+ * a 64-bit little-endian profile-0 payload: frad_p0_digital(coeffs_out, N*C*8, n_frames, N, C, 64, FRAD_LITTLE_ENDIAN)
+ * finishes profile2.digital with idct(norm='forward').  bits: one of profile2.DEPTHS (8, 10, 12, 14, 16, 20, 24), else
+ * FRAD_E_INVALID; N a compact frame size, 1 <= C <= 64.
+ * Deviation on damaged streams only: frad_p0_digital turns NaN / +-Inf coefficients into 0 (profile0.py:64), where
+ * profile2.digital hands them to the IDCT; only a corrupt threshold code makes them. */
+int frad_p2_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_frames, int32_t N, int32_t C,
+                          int32_t* q, int32_t* tq, int32_t* lpc, int32_t* status, void* stream);
+int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
+                  int32_t srate, double* coeffs_out, void* stream);
+
 /* ---- frame header checksum (row 8f #1) --------------------------------------------------------
  * crc_out[i] = zlib.crc32 of the `nbytes` payload bytes of frame i (at data + i*stride), the value
  * ASFH.write puts into a lossless frame's header (src/libfrad/tools/asfh.py:51-73), so a batch's
