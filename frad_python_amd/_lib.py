@@ -49,6 +49,10 @@ SYMBOLS = {
     "frad_p1_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "frad_p2_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "frad_p2_synth": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_p2_analogue": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_double, c_uint32,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p2_golomb_bound": (c_size_t, [c_int32, c_int32]),
+    "frad_p2_golomb_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "frad_from_f64": (c_int, [c_void_p, c_int64, c_int32, c_uint32, c_void_p, c_void_p]),
     "frad_p0_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
     "frad_p4_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
@@ -170,6 +174,16 @@ class FradLib:
 
     def p2_synth(self, q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream=0):
         self._check(self.dll.frad_p2_synth(q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream))
+
+    def p2_analogue(self, pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate, loss_level, flags, q, tq, lpc, stream=0):
+        self._check(self.dll.frad_p2_analogue(pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate, loss_level, flags,
+                                              q, tq, lpc, stream))
+
+    def p2_golomb_bound(self, N, C):
+        return int(self.dll.frad_p2_golomb_bound(N, C))
+
+    def p2_golomb_encode(self, q, tq, lpc, n_frames, N, C, bodies, body_stride, body_bytes, stream=0):
+        self._check(self.dll.frad_p2_golomb_encode(q, tq, lpc, n_frames, N, C, bodies, body_stride, body_bytes, stream))
 
     def from_f64(self, pcm, n_values, out_dtype, out, stream=0, flags=FRAD_RAW_BE_INTS):
         self._check(self.dll.frad_from_f64(pcm, n_values, out_dtype, flags, out, stream))

@@ -133,6 +133,16 @@ class HipBridge:
         host = self._down_bytes(flat) if flat.numel() else b""
         return [host[off[i]:off[i + 1]] for i in range(n_frames)]
 
+    def p2_encode_bodies(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
+        """``p1_encode_bodies`` for profile 2: DCT, masking, TNS analysis, quantiser and the three-stream Golomb coder on the
+        device (profile2.py:15-52), one D2H copy of exactly the body bytes."""
+        q, tq, lpc = self.core.p2_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
+                                                 frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
+        flat, offsets = self.core.p2_golomb_encode_batch(q, tq, lpc)
+        off = offsets.cpu().numpy()
+        host = self._down_bytes(flat) if flat.numel() else b""
+        return [host[off[i]:off[i + 1]] for i in range(n_frames)]
+
     def p1_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
         """Inflated frame bodies -> PCM: Golomb decode (profile1.py:59-64) and K8 on the device, one H2D copy of the
         bodies (about a byte per coefficient instead of the four of an int32 array)."""

@@ -347,7 +347,7 @@ def p1_digital_batch(q: torch.Tensor, tq: torch.Tensor, N: int, C: int, bits: in
 
 
 # ---------------------------------------------------------------------------------------------
-# profile 2 (TNS): decode only (the reference's encoder refuses profile 2, fourier/__init__.py AVAILABLE)
+# profile 2 (TNS): decode, and encode behind Encoder(..., allow_profile2=True) (the reference's encoder refuses profile 2)
 # ---------------------------------------------------------------------------------------------
 P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)                # ref: fourier/profile2.py:7
 P2_LPC = 13                                            # MAX_ORDER + 1 integers per channel (tools/p2tools.py:4)
@@ -390,6 +390,60 @@ def p2_synth_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor, N: int,
     with torch.cuda.device(q.device):
         _lib.load().p2_synth(q.data_ptr(), tq.data_ptr(), lpc.data_ptr(), n_frames, N, C, bits, srate, out.data_ptr(), _stream_ptr())
     return out
+
+
+def p2_analogue_batch(pcm: torch.Tensor, pcm_format: str, n_frames: int, N: int, C: int, bits: int, srate: int,
+                      loss_level: float, *, frame_stride: int | None = None, n_valid: int | None = None,
+                      raw_be_ints: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``profile2.analogue`` up to the Exp-Golomb coder (profile2.py:15-46), batched: frame geometry as ``p1_analogue_batch``;
+    ``bits`` one of ``P2_DEPTHS`` (the caller maps any other depth to 16, profile2.py:16).  Returns ``q`` int32 [n_frames, N, C],
+    ``tq`` int32 [n_frames, 27, C] and ``lpc`` int32 [n_frames, 13, C] -- the layout ``p2_synth_batch`` reads."""
+    if bits not in P2_DEPTHS:
+        raise ValueError(f"profile 2 depth must be one of {P2_DEPTHS}, got {bits}")
+    if not 1 <= C <= 64:
+        raise ValueError(f"profile 2 takes 1 to 64 channels, got {C}")
+    code = pcm_dtype_code(pcm_format)
+    hop = N if frame_stride is None else frame_stride
+    nv = N if n_valid is None else n_valid
+    if n_frames < 0 or hop < 0 or not 0 <= nv <= N:
+        raise ValueError(f"bad frame geometry: n_frames={n_frames} frame_stride={hop} n_valid={nv} N={N}")
+    need = ((n_frames - 1) * hop + nv) * C * itemsize_of(code) if n_frames else 0
+    if pcm.numel() * pcm.element_size() < need:
+        raise ValueError(f"pcm holds {pcm.numel() * pcm.element_size()} bytes, {need} needed")
+    _require_cuda(pcm, "pcm")
+    q = torch.empty((n_frames, N, C), dtype=torch.int32, device=pcm.device)
+    tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=pcm.device)
+    lpc = torch.empty((n_frames, P2_LPC, C), dtype=torch.int32, device=pcm.device)
+    flags = int(raw_be_ints) * _lib.FRAD_RAW_BE_INTS
+    with torch.cuda.device(pcm.device):
+        _lib.load().p2_analogue(pcm.data_ptr(), code, n_frames, N, C, hop, nv, bits, srate, float(loss_level), flags,
+                                q.data_ptr(), tq.data_ptr(), lpc.data_ptr(), _stream_ptr())
+    return q, tq, lpc
+
+
+def p2_golomb_encode_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The Exp-Golomb-Rice stage of ``profile2.analogue`` (profile2.py:48-52) on the device: ``(bodies uint8 [total], offsets
+    int64 [n_frames + 1])``, frame i's pre-deflate body ('>H' len + Golomb(lpc) + '>I' len + Golomb(tq) + Golomb(q)) at
+    ``bodies[offsets[i]:offsets[i+1]]``.  Deflate stays on the host."""
+    if q.dtype != torch.int32 or q.dim() != 3 or not q.is_contiguous():
+        raise TypeError("q must be a contiguous int32 tensor [n_frames, N, C]")
+    n_frames, N, C = q.shape
+    _require_int32(tq, (n_frames, P1_BANDS, C), "tq")
+    _require_int32(lpc, (n_frames, P2_LPC, C), "lpc")
+    _require_cuda(q, "q"); _require_cuda(tq, "tq"); _require_cuda(lpc, "lpc")
+    lib = _lib.load()
+    stride = lib.p2_golomb_bound(N, C)
+    rows = torch.empty((n_frames, stride), dtype=torch.uint8, device=q.device)
+    nbytes = torch.empty(n_frames, dtype=torch.int64, device=q.device)
+    offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=q.device)
+    with torch.cuda.device(q.device):
+        lib.p2_golomb_encode(q.data_ptr(), tq.data_ptr(), lpc.data_ptr(), n_frames, N, C, rows.data_ptr(), stride, nbytes.data_ptr(),
+                             _stream_ptr())
+        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, 0, offsets.data_ptr(), _stream_ptr())
+        total = int(offsets[-1].item()) if n_frames else 0      # the one host read: the size of the result
+        out = torch.empty(total, dtype=torch.uint8, device=q.device)
+        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, out.data_ptr(), offsets.data_ptr(), _stream_ptr())
+    return out, offsets
 
 
 def p2_digital_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor, N: int, C: int, bits: int, srate: int) -> torch.Tensor:

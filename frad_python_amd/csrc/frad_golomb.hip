@@ -175,14 +175,49 @@ __device__ __forceinline__ long long encode_stream_wave(WaveSink& s, long long p
     return (pos + 7) & ~7LL;                                   // bitstr2bytes pads with zeros
 }
 
+// byte length of one coded stream (k byte + codes, zero-padded), for a header that precedes it; wave-wide
+__device__ __forceinline__ long long stream_bytes_wave(const int32_t* __restrict__ data, long long n) {
+    const int lane = threadIdx.x & 63;
+    u64 dmax = 0;
+    for (long long i = lane; i < n; i += 64) { const long long v = data[i]; const u64 a = (u64)(v < 0 ? -v : v); dmax = a > dmax ? a : dmax; }
+    const int k = rice_k(wave_max_u64(dmax));
+    u64 bits = 0;
+    for (long long i = lane; i < n; i += 64) bits += ((zigzag(data[i]) + (1ull << k)) >> (k + 1)) ? k + 3 : k + 1;
+    bits = wave_allreduce_u64(bits, [](u64 a, u64 b) { return a + b; });
+    return 1 + (long long)((bits + 7) >> 3);
+}
+// `nb` <= 32 header bits `v` at bit `pos` (byte aligned, within the two words after s.base); one lane
+__device__ __forceinline__ void wsink_put_header(WaveSink& s, long long pos, uint32_t v, int nb) {
+    const int rel = (int)(pos - s.base), w = rel >> 5, sh = rel & 31;
+    const u64 bits = ((u64)v << (64 - nb)) >> sh;                  // MSB-first from bit sh of word w
+    atomicOr(&s.words[w], (int)(uint32_t)(bits >> 32));
+    if ((uint32_t)bits) atomicOr(&s.words[w + 1], (int)(uint32_t)bits);
+}
+
+// lpc == NULL: profile 1's body  '>I' len | Golomb(tq) | Golomb(q).  Otherwise profile 2's (profile2.py:46-49)
+//   '>H' len | Golomb(lpc) | '>I' len | Golomb(tq) | Golomb(q): both lengths are measured before the coding starts
 __global__ void __launch_bounds__(64) k_gol_encode(const int32_t* __restrict__ q, const int32_t* __restrict__ tq, long long nq, long long ntq,
-                                                   unsigned char* __restrict__ body, long long stride, long long* __restrict__ nbytes) {
+                                                   unsigned char* __restrict__ body, long long stride, long long* __restrict__ nbytes,
+                                                   const int32_t* __restrict__ lpc, long long nl) {
     FRAD_DYN_SMEM(smem);                                      // GOL_LDS bytes: the word buffer
     int* words = reinterpret_cast<int*>(smem);
     const long long f = blockIdx.x;
     WaveSink s{words, body + f * stride, 0};
     for (int i = threadIdx.x; i < GWORDS; i += 64) words[i] = 0;
     FRAD_LDS_BARRIER();
+    if (lpc != nullptr) {
+        const long long lb = stream_bytes_wave(lpc + f * nl, nl), tb = stream_bytes_wave(tq + f * ntq, ntq);
+        if (threadIdx.x == 0) wsink_put_header(s, 0, (uint32_t)lb, 16);
+        FRAD_LDS_BARRIER();
+        const long long end_l = encode_stream_wave(s, 16, lpc + f * nl, nl);
+        if (threadIdx.x == 0) wsink_put_header(s, end_l, (uint32_t)tb, 32);
+        FRAD_LDS_BARRIER();
+        const long long end_t = encode_stream_wave(s, end_l + 32, tq + f * ntq, ntq);
+        const long long end_q = encode_stream_wave(s, end_t, q + f * nq, nq);
+        wsink_flush(s, end_q, true);
+        if (threadIdx.x == 0) nbytes[f] = end_q >> 3;
+        return;
+    }
     // '>I' len(thres_gol) is only known once that stream is coded: it goes first, so code the thresholds from bit 32
     // on and patch the length in afterwards (the first word has left LDS by then)
     const long long end_t = encode_stream_wave(s, 32, tq + f * ntq, ntq);
@@ -795,7 +830,27 @@ int frad_p1_golomb_encode(const int32_t* q, const int32_t* tq, int64_t n_frames,
     if (body_stride < (int64_t)frad_p1_golomb_bound(N, C) || (body_stride & 3) || (reinterpret_cast<uintptr_t>(bodies) & 3)) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_gol_encode, dim3((unsigned)n_frames), dim3(64), GOL_LDS, static_cast<hipStream_t>(stream), q, tq, (long long)N * C, 27LL * C,
-                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes));
+                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes),
+                       static_cast<const int32_t*>(nullptr), 0LL);
+    GOLCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+size_t frad_p2_golomb_bound(int32_t N, int32_t C) {
+    if (N < 1 || C < 1) return 0;
+    const size_t nl = 13 * (size_t)C;
+    return frad_p1_golomb_bound(N, C) + (2 + 1 + (nl * 35 + 7) / 8 + 15) / 16 * 16;
+}
+
+int frad_p2_golomb_encode(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C,
+                          void* bodies, int64_t body_stride, int64_t* body_bytes, void* stream) {
+    if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
+    if (n_frames == 0) return FRAD_OK;
+    if (!q || !tq || !lpc || !bodies || !body_bytes) return FRAD_E_INVALID;
+    if (body_stride < (int64_t)frad_p2_golomb_bound(N, C) || (body_stride & 3) || (reinterpret_cast<uintptr_t>(bodies) & 3)) return FRAD_E_INVALID;
+    if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_gol_encode, dim3((unsigned)n_frames), dim3(64), GOL_LDS, static_cast<hipStream_t>(stream), q, tq, (long long)N * C, 27LL * C,
+                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes), lpc, 13LL * C);
     GOLCHK(hipGetLastError());
     return FRAD_OK;
 }

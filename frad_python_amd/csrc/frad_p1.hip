@@ -328,6 +328,52 @@ int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64
     return FRAD_OK;
 }
 
+int frad_p2_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32_t N, int32_t C, int64_t frame_stride,
+                     int32_t n_valid, int32_t bits, int32_t srate, double loss_level, uint32_t flags,
+                     int32_t* q, int32_t* tq, int32_t* lpc, void* stream) {
+    if (n_frames < 0 || C < 1 || C > 64 || !legal_compact_size(N) || n_valid < 0 || n_valid > N || frame_stride < 0) return FRAD_E_INVALID;
+    if (pcm_dtype < 0 || pcm_dtype > 23) return FRAD_E_INVALID;
+    bool depth = false;
+    for (int b : {8, 10, 12, 14, 16, 20, 24}) depth |= b == bits;       // profile2.py:7 DEPTHS
+    if (!depth) return FRAD_E_INVALID;
+    const int kind = pcm_dtype >> 3, lg = (pcm_dtype >> 1) & 3;
+    if ((kind == 2 && lg == 0) || (lg == 0 && (pcm_dtype & 1))) return FRAD_E_INVALID;
+    if (n_frames == 0) return FRAD_OK;
+    if (!pcm || !q || !tq || !lpc) return FRAD_E_INVALID;
+    if (n_frames > 0x7fffffffLL / C) return FRAD_E_UNSUPPORTED;
+    P1Tables tb;
+    int rc = make_tables(N, srate, 16, loss_level, tb);
+    if (rc != FRAD_OK) return rc;
+    tb.scale = ldexp(1.0, bits - 1);                                       // profile2.py:9-10 (profile 1's depth table does not apply)
+    tb.f32 = (kind == 2 && lg <= 2) ? 1 : 0;                               // float32 / float16 PCM: float32 DCT and band statistics
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    struct Scratch { hipStream_t s; void* p = nullptr; ~Scratch() { if (p) (void)hipFreeAsync(p, s); } } plane{s}, padded{s};
+    const size_t item = (size_t)1 << lg;
+    const void* src = pcm;
+    long long stride = frame_stride;
+    if (n_valid < N) {                                                     // frames shorter than N: zero-padded copies (profile2.py:20)
+        const size_t row = (size_t)N * C * item;
+        if (hipMallocAsync(&padded.p, row * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+        P1CHK(hipMemsetAsync(padded.p, 0, row * (size_t)n_frames, s));
+        if (n_valid > 0)
+            P1CHK(hipMemcpy2DAsync(padded.p, row, pcm, (size_t)frame_stride * C * item, (size_t)n_valid * C * item, (size_t)n_frames,
+                                   hipMemcpyDeviceToDevice, s));
+        src = padded.p; stride = N;
+    }
+    // stage A: the float64 DCT plane (norm='forward') -- profile 0's transform at 64-bit little-endian storage
+    const size_t pbytes = (size_t)N * C * 8;
+    if (hipMallocAsync(&plane.p, pbytes * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+    rc = frad_p0_analogue(src, pcm_dtype, n_frames, N, C, stride, 64, FRAD_LITTLE_ENDIAN | (flags & FRAD_RAW_BE_INTS), plane.p,
+                          (int64_t)pbytes, nullptr, stream);
+    if (rc != FRAD_OK) return rc;
+    // stage B: thresholds, masking, TNS analysis, quantiser
+    const size_t lds = (size_t)p2_analysis_lds(N);
+    hipLaunchKernelGGL(k_p2_analysis<0>, dim3((unsigned)(n_frames * C)), dim3(P2_THREADS), lds, s, static_cast<double*>(plane.p), q, tq, lpc,
+                       (long long)n_frames, N, C, tb);
+    P1CHK(hipGetLastError());
+    return FRAD_OK;
+}
+
 }  // extern "C"
 namespace frad {
 // frad_p1_digital, optionally with the decoder's output conversion applied by the kernel's own store (frad_p1_digital_pcm):

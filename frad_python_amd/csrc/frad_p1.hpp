@@ -431,6 +431,198 @@ __global__ void __launch_bounds__(64) k_p2_synth(const int32_t* __restrict__ q, 
     }
 }
 
+// profile 2 analysis (fourier/profile2.py:15-55, tools/p2tools.py:55-103): per (frame, channel) the 27 masking thresholds
+// and the divisor ramp of profile 1, the masked spectrum m = X / div, then tns_analysis -- the order-12 LPC of m and, when
+// it predicts well, the FIR residual in its place -- and the power-law quantiser.  One block per (frame, channel) over the
+// float64 DCT plane [n_frames, N, C] that frad_p0_analogue wrote (norm='forward'); m overwrites X in place (each block owns
+// its column), and every later pass reads it back through L2: a channel's spectrum at N = 28 672 is 224 KiB, more than a
+// CU's LDS, so one code path serves all 32 compact sizes.  Reductions are block sums (wave sums, then the wave partials in
+// order), not numpy's pairwise order: they decide only comparisons and the LPC's rounding.  The
+// Levinson-Durbin recursion runs on one lane, in float64, with the reference's 0.96 clamp and early exits.  The residual is
+// np.convolve's (scipy.signal.lfilter routes a FIR filter there): on the reference platform a sequential fused multiply-add
+// from the oldest tap, r[k] = fma(b12, m[k-12], ... fma(b1, m[k-1], 0)) + m[k] -- reproduced here bit for bit.
+constexpr int P2_THREADS = 256;
+constexpr int P2_RED = (P2_ORDER + 1) * (P2_THREADS / 64 + 1);             // doubles of the block-sum scratch
+
+// block sums of P values per thread; every thread gets the totals.  red: P2_RED doubles of LDS
+template <int P>
+__device__ __forceinline__ void p2_block_sum(double (&v)[P], double* red) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int p = 0; p < P; ++p) { const double s = wave_sum_f64(v[p]); if (lane == 0) red[wave * P + p] = s; }
+    __syncthreads();
+    if (threadIdx.x < P) { double s = 0.0; for (int w = 0; w < nw; ++w) s += red[w * P + threadIdx.x]; red[nw * P + threadIdx.x] = s; }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < P; ++p) v[p] = red[nw * P + p];
+    __syncthreads();
+}
+__device__ __forceinline__ double p2_block_max(double v, double* red) {            // v >= 0 (or NaN, which fmax drops)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    v = u2d(wave_allreduce_u64(d2u(v), [](u64 a, u64 b) { return d2u(fmax(u2d(a), u2d(b))); }));
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int w = 0; w < nw; ++w) r = fmax(r, red[w]);
+    __syncthreads();
+    return r;
+}
+// numpy's sum of n <= 12 float64 values (pairwise_sum below its block size: a plain loop under 8 values, else 8 partial
+// sums combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) and the rest added in order)
+__device__ __forceinline__ double p2_np_sum(const double* a, int n) {
+    if (n < 8) { double s = 0.0; for (int i = 0; i < n; ++i) s += a[i]; return s; }
+    double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    for (int i = 8; i < n; ++i) s += a[i];
+    return s;
+}
+// levinson_durbin + quantise_lpc (p2tools.py:17-50): r[0..12] -> lq[0..12] (lq[0] = 0); false = tns_analysis gives up here
+__device__ __forceinline__ bool p2_levinson(const double* r, int* lq) {
+    double lpc[P2_ORDER + 1], tmp[P2_ORDER + 1], prod[P2_ORDER];
+    lpc[0] = 1.0;
+    for (int i = 1; i <= P2_ORDER; ++i) lpc[i] = 0.0;
+    double err = r[0];
+    if (err > 1e-10) {
+        for (int i = 1; i <= P2_ORDER; ++i) {
+            for (int j = 0; j < i; ++j) prod[j] = lpc[j] * r[i - j];
+            double refl = -p2_np_sum(prod, i) / err;
+            if (fabs(refl) >= 0.96) refl = refl > 0 ? 0.96 : -0.96;        // 0.96 * np.sign (NaN cannot reach here)
+            for (int j = 0; j <= P2_ORDER; ++j) tmp[j] = lpc[j];
+            lpc[i] = refl;
+            for (int j = 1; j < i; ++j) lpc[j] += refl * tmp[i - j];
+            err *= 1.0 - refl * refl;
+            if (err <= 1e-12) break;
+        }
+    }
+    for (int j = 0; j < P2_ORDER; ++j) prod[j] = fabs(lpc[j + 1]);
+    if (!(p2_np_sum(prod, P2_ORDER) >= 0.01)) return false;               // np.sum(np.abs(lpc[1:])) < 0.01
+    bool any = false;
+    lq[0] = 0;
+    for (int j = 1; j <= P2_ORDER; ++j) {
+        double v = lpc[j] * 15.0;
+        v = v < -15.0 ? -15.0 : (v > 14.0 ? 14.0 : v);                    // np.clip, then round half to even
+        lq[j] = (int)rint(v);
+        any |= lq[j] != 0;
+    }
+    return any;
+}
+// the FIR residual at bin k of the masked column m (stride C); b[1..12] = lq / 15
+__device__ __forceinline__ double p2_residual(const double* __restrict__ m, int C, int k, const double* b) {
+    double acc = 0.0;
+    const int i0 = k < P2_ORDER ? k : P2_ORDER;
+    for (int i = i0; i >= 1; --i) acc = fma(b[i], m[(long long)(k - i) * C], acc);
+    return m[(long long)k * C] + acc;
+}
+
+template <int UNUSED>
+__global__ void __launch_bounds__(P2_THREADS) k_p2_analysis(double* __restrict__ X, int32_t* __restrict__ q, int32_t* __restrict__ tq,
+                                                            int32_t* __restrict__ lpc, long long n_frames, int N, int C, P1Tables tb) {
+    FRAD_DYN_SMEM(smem);
+    double* red = reinterpret_cast<double*>(smem);                       // P2_RED doubles
+    double* bco = red + P2_RED;                                          // b[0..12] of the FIR; bco[13] = use-TNS flag
+    int* lqs = reinterpret_cast<int*>(bco + 16);                         // the 13 LPC integers
+    unsigned char* scratch = reinterpret_cast<unsigned char*>(lqs + 16);  // P1Lds for one channel
+    const long long g = blockIdx.x;
+    const long long f = g / C;
+    const int c = (int)(g - f * C), wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    double* x = X + f * (long long)N * C + c;
+    const P1Lds l = p1_lds(scratch, 1);
+    p1_tables_to_lds(scratch, 1, tb, N);
+    __syncthreads();
+    // band energies of X * 2^(bits-1) and the thresholds, as profile 1's quantiser (p1_quantise)
+    for (int b = wave; b < P1_BANDS; b += nw) {
+        const int a = l.edge[b], e = l.edge[b + 1];
+        double acc = 0.0;
+        if (tb.f32) for (int k = a + lane; k < e; k += 64) { const float v = (float)x[(long long)k * C] * (float)tb.scale; acc += (double)(v * v); }
+        else for (int k = a + lane; k < e; k += 64) { const double v = x[(long long)k * C] * tb.scale; acc = fma(v, v, acc); }
+        acc = wave_sum_f64(acc);
+        if (lane == 0) l.thres[b] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < P1_BANDS) {
+        const int b = threadIdx.x;
+        l.thres[b] = b < tb.nb_used ? p1_band_threshold(l.thres[b], l.edge[b + 1] - l.edge[b], l.floor_[b], tb.loss, tb.f32) : 0.0;
+    }
+    __syncthreads();
+    p1_ramp_steps(l, 1);
+    if (threadIdx.x < P1_BANDS) {
+        const int b = threadIdx.x;
+        const double t = l.thres[b];
+        const double v = log(t > 1.0 ? t : 1.0) / log(2.718281828459045 / 2);
+        tq[f * (long long)(P1_BANDS * C) + b * C + c] = (int32_t)rint(copysign(pow(fabs(v), 1.0 / 0.75), v));
+    }
+    __syncthreads();
+    // m = X / div in place (div 0 = inf, profile2.py:31); the statistics of lpc_cond and the energy test on the way
+    double s1[4] = {0.0, 0.0, 0.0, 0.0};                                 // sum m, sum |m|, sum log(|m| + 1e-10), sum m^2
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+        double v = x[(long long)k * C];
+        if (tb.f32) v = (double)(float)v;
+        const double div = p1_spread(l, 0, k);
+        v = v / (div == 0.0 ? (double)INFINITY : div);
+        x[(long long)k * C] = v;
+        s1[0] += v; s1[1] += fabs(v); s1[2] += log(fabs(v) + 1e-10); s1[3] = fma(v, v, s1[3]);
+    }
+    p2_block_sum<4>(s1, red);                                            // (its barriers also publish m to the block)
+    const double dn = (double)N;
+    const double mean = s1[0] / dn;
+    bool tns = N >= 2 * P2_ORDER && exp(s1[2] / dn) / (s1[1] / dn + 1e-10) < 0.5 && !(s1[3] < 1e-10);
+    double oe = 0.0;                                                     // sum (m - mean)^2: calc_autocorr's norm and predgain's
+    if (tns) {
+        double s2[1] = {0.0};
+        for (int k = threadIdx.x; k < N; k += blockDim.x) { const double d = x[(long long)k * C] - mean; s2[0] = fma(d, d, s2[0]); }
+        p2_block_sum<1>(s2, red);
+        oe = s2[0];
+        const double nrm = sqrt(oe), dv = nrm > 1e-6 ? nrm : 1.0;
+        double r[P2_ORDER + 1];
+#pragma unroll
+        for (int i = 0; i <= P2_ORDER; ++i) r[i] = 0.0;
+        for (int k = threadIdx.x; k < N; k += blockDim.x) {
+            const double sk = (x[(long long)k * C] - mean) / dv;
+#pragma unroll
+            for (int i = 0; i <= P2_ORDER; ++i)
+                if (k + i < N) r[i] = fma(sk, (x[(long long)(k + i) * C] - mean) / dv, r[i]);
+        }
+        p2_block_sum<P2_ORDER + 1>(r, red);
+        if (threadIdx.x == 0) {
+            for (int i = 0; i <= P2_ORDER; ++i) { const double w = (double)i * 0.01; r[i] *= exp(-0.5 * (w * w)); }
+            const bool ok = p2_levinson(r, lqs);
+            bco[0] = 1.0;
+            for (int i = 1; i <= P2_ORDER; ++i) bco[i] = (double)lqs[i] / 15.0;
+            bco[P2_ORDER + 1] = ok ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        tns = bco[P2_ORDER + 1] != 0.0;
+    }
+    if (tns) {                                                           // the residual: finite, <= 1e6, and a prediction gain
+        double s3[2] = {0.0, 0.0};                                       // non-finite count, sum r
+        double mx = 0.0;
+        for (int k = threadIdx.x; k < N; k += blockDim.x) {
+            const double rv = p2_residual(x, C, k, bco);
+            s3[0] += isfinite(rv) ? 0.0 : 1.0;
+            s3[1] += rv;
+            mx = fmax(mx, fabs(rv));
+        }
+        p2_block_sum<2>(s3, red);
+        mx = p2_block_max(mx, red);
+        tns = s3[0] == 0.0 && mx <= 1e6;
+        if (tns) {
+            const double rmean = s3[1] / dn;
+            double s4[1] = {0.0};
+            for (int k = threadIdx.x; k < N; k += blockDim.x) { const double d = p2_residual(x, C, k, bco) - rmean; s4[0] = fma(d, d, s4[0]); }
+            p2_block_sum<1>(s4, red);
+            const double re = s4[0];
+            const double gain = (oe < 1e-10 || re < 1e-10 || re >= oe) ? 0.0 : 20.0 * log10(oe / re);
+            tns = gain >= 0.030102999566398120;                          // MIN_PRED = log10(2) / 10
+        }
+    }
+    if (threadIdx.x <= P2_ORDER) lpc[f * (long long)((P2_ORDER + 1) * C) + (long long)threadIdx.x * C + c] = tns ? lqs[threadIdx.x] : 0;
+    int32_t* qc = q + f * (long long)N * C + c;
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+        const double v = tns ? p2_residual(x, C, k, bco) : x[(long long)k * C];
+        qc[(long long)k * C] = p1w_quantise(v, 1.0, tb.scale);
+    }
+}
+__host__ __device__ constexpr int p2_analysis_lds(int N) { return (P2_RED + 16) * 8 + 16 * 4 + p1_scratch_bytes(1, N); }
+
 // R8: decoder overlap-add over a batch of consecutive frames (decoder.py:28-46).  Frame i keeps
 // rows [0, cut) -- its first L = N - cut rows cross-faded with frame i-1's tail -- and hands its
 // own tail [cut, N) to frame i+1.  out: [n_frames, cut, C]; next_tail: [L, C].

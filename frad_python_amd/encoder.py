@@ -17,6 +17,7 @@ from .tools.asfh import ASFH
 
 _LOSSLESS_DEPTHS = (12, 16, 24, 32, 48, 64)
 _P1_DEPTHS = (8, 12, 16, 24, 32, 48, 64)
+_P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)        # fourier/profile2.py:7
 
 
 _POOL = None
@@ -50,8 +51,11 @@ class EncodeResult:
 
 
 class Encoder:
-    def __init__(self, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *, bridge=None):
-        if profile not in AVAILABLE:
+    def __init__(self, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *, bridge=None,
+                 allow_profile2: bool = False):
+        # profile 2 (TNS) is outside the reference's AVAILABLE list; `allow_profile2=True` admits it on this instance only
+        self.allow_profile2 = bool(allow_profile2)
+        if profile not in AVAILABLE and not (profile == 2 and self.allow_profile2):
             print(f"Invalid profile! Available: {AVAILABLE}", file=sys.stderr)
             sys.exit(1)
         self.asfh = ASFH()
@@ -91,7 +95,15 @@ class Encoder:
         """n_frames frames of n_eff sample-frames, frame i starting i*hop sample-frames into `pcm`."""
         prof, C = self.asfh.profile, self.channels
         out = []
-        if prof == 1:
+        if prof == 2:
+            bits = self.bit_depth if self.bit_depth in _P2_DEPTHS else 16                    # profile2.py:16
+            N = compact.get_samples_min_ge(n_eff)
+            # DCT, masking, TNS analysis, quantiser and the three Golomb streams on the device; the host deflates and frames
+            bodies = self.bridge.p2_encode_bodies(pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate),
+                                                  self.loss_level, hop, n_valid)
+            for frad in _map_zlib(self._deflate, bodies):
+                out.append(self._emit(frad, _P2_DEPTHS.index(bits), n_valid))
+        elif prof == 1:
             bits = self.bit_depth if self.bit_depth in _P1_DEPTHS else 16
             N = compact.get_samples_min_ge(n_eff)
             # quantiser and Exp-Golomb-Rice coder behind the bridge (on the device); the host only deflates (profile1.py:50) and frames
@@ -191,7 +203,8 @@ class Encoder:
         return self.asfh.profile
 
     def set_profile(self, profile, srate, channels, bit_depth, frame_size):
-        for e in (self.verify_profile(profile), self.verify_srate(profile, srate), self.verify_channels(profile, channels),
+        e_prof = None if (profile == 2 and getattr(self, "allow_profile2", False)) else self.verify_profile(profile)
+        for e in (e_prof, self.verify_srate(profile, srate), self.verify_channels(profile, channels),
                   self.verify_bit_depth(profile, bit_depth), self.verify_frame_size(profile, frame_size)):
             if e is not None:
                 return e

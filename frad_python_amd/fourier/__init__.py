@@ -1,7 +1,7 @@
 """Validation tables of the transform core (mirror of src/libfrad/fourier/__init__.py:3-25).
 
-Profile 2 ("in development" upstream, not in AVAILABLE there either) is decoded but not encoded: the reference's
-Encoder refuses it too."""
+Profile 2 ("in development" upstream, not in AVAILABLE there either) is decoded; it is encoded only by an
+Encoder(..., allow_profile2=True), since the reference's Encoder refuses it."""
 from . import profiles
 
 AVAILABLE = [0, 1, 4]

@@ -205,6 +205,36 @@ int frad_p2_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_
 int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
                   int32_t srate, double* coeffs_out, void* stream);
 
+/* ---- profile 2 (TNS) encode: fourier/profile2.py:15-55, tools/p2tools.py:55-103 ------------------------------------------
+ * frad_p2_analogue == profile2.analogue up to the three integer arrays.  Geometry as frad_p1_analogue (N a compact frame size,
+ * frame i reads `n_valid` <= N sample-frames at pcm + i*frame_stride, zero-padded to N), 1 <= C <= 64; bits one of
+ * profile2.DEPTHS (8, 10, 12, 14, 16, 20, 24), else FRAD_E_INVALID (the caller applies `bits not in DEPTHS -> 16`).
+ *   q    int32 [n_frames, N, C]   bin-major / channel-minor  (freqs_flat, profile2.py:38-40)
+ *   tq   int32 [n_frames, 27, C]  band-major / channel-minor (thres_flat, profile2.py:42-44)
+ *   lpc  int32 [n_frames, 13, C]  the quantised LPC, lpc[:, 0, :] == 0, all 13 zero where tns_analysis keeps the masked
+ *        spectrum (lpc_flat, profile2.py:46)
+ * exactly the layout frad_p2_golomb_decode writes, so the three arrays go to frad_p2_synth as they are.  The DCT is profile 0's
+ * (frad_p0_analogue at 64-bit little-endian storage, into stream-ordered scratch of n_frames*N*C*8 bytes); the masking, the
+ * TNS analysis and the quantiser run in k_p2_analysis, one block per (frame, channel).
+ * Parity: the thresholds and the LPC integers are the reference's, the quantised coefficients profile 1's contract (|dq| <= 1
+ * on a small fraction of values: the transform is not pocketfft's).  Deviations, all in the last bits of quantities that are
+ * only compared or rounded: the band energies, the means of lpc_cond / calc_autocorr / predgain and the autocorrelation are
+ * block sums, not numpy's pairwise sums or np.correlate's BLAS dot products; a frame whose statistic lands within a few ulps of
+ * one of tns_analysis's thresholds (1e-10, 0.5, 0.01, 1e6, MIN_PRED) or an LPC value within an ulp of a rounding boundary can
+ * decide differently.  The FIR residual itself is np.convolve's arithmetic bit for bit (a sequential fused multiply-add from
+ * the oldest tap, as the reference platform's BLAS dot computes it).
+ *
+ * frad_p2_golomb_encode == the three exp_golomb_rice_encode calls and the struct.pack of profile2.py:48-52: per frame the
+ * pre-deflate body  '>H' len(lpc_gol) | lpc_gol | '>I' len(thres_gol) | thres_gol | freqs_gol  at bodies + i*body_stride, its
+ * length in body_bytes[i]; body_stride >= frad_p2_golomb_bound(N, C), a multiple of 4, `bodies` 4-byte aligned.  The rows
+ * go to frad_rows_compact as profile 1's do; deflate stays on the host. */
+int frad_p2_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32_t N, int32_t C, int64_t frame_stride,
+                     int32_t n_valid, int32_t bits, int32_t srate, double loss_level, uint32_t flags,
+                     int32_t* q, int32_t* tq, int32_t* lpc, void* stream);
+size_t frad_p2_golomb_bound(int32_t N, int32_t C);
+int frad_p2_golomb_encode(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C,
+                          void* bodies, int64_t body_stride, int64_t* body_bytes, void* stream);
+
 /* ---- frame header checksum (row 8f #1) --------------------------------------------------------
  * crc_out[i] = zlib.crc32 of the `nbytes` payload bytes of frame i (at data + i*stride), the value
  * ASFH.write puts into a lossless frame's header (src/libfrad/tools/asfh.py:51-73), so a batch's
