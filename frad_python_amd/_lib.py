@@ -61,6 +61,8 @@ SYMBOLS = {
     "frad_rs_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "frad_rs_repair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "frad_rs_encode_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "frad_crc16_ansi_frames": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "frad_bench_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
@@ -220,6 +222,12 @@ class FradLib:
     def rs_repair(self, data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected, failed, work, stream=0):
         self._check(self.dll.frad_rs_repair(data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected,
                                             failed, work, stream))
+
+    def rs_encode_frames(self, data, in_stride, n_frames, nbytes, dsize, codesize, out, out_stride, stream=0):
+        self._check(self.dll.frad_rs_encode_frames(data, in_stride, n_frames, nbytes, dsize, codesize, out, out_stride, stream))
+
+    def crc16_ansi_frames(self, data, offsets, n_frames, out, stream=0):
+        self._check(self.dll.frad_crc16_ansi_frames(data, offsets, n_frames, out, stream))
 
     def bench_copy(self, src, dst, nbytes, stream=0):
         self._check(self.dll.frad_bench_copy(src, dst, nbytes, stream))

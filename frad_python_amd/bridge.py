@@ -58,26 +58,31 @@ class HipBridge:
         return out
 
     def lossless_encode_stream(self, profile, pcm: bytes, fmt, n_frames, N, C, bits, little_endian, head_fn,
-                               raw_be_ints=True):
+                               raw_be_ints=True, ecc_ratio=None):
         """Whole batch -> finished stream bytes, assembled on the device: the payload kernel writes every
         frame behind a 32-byte hole, ``frad_crc32_frames`` fills in the checksums, the constant part of the
         header (``head_fn(payload_bytes)`` -> 28 bytes, tools/asfh.py) is broadcast, and one D2H copy returns
-        the result.  None when a frame needs a deeper format or a 64-bit length: the caller then goes frame
-        by frame through ``lossless_encode``."""
+        the result.  With ``ecc_ratio`` = (dsize, codesize) the payload kernel writes into scratch instead and
+        ``frad_rs_encode_frames`` writes the protected payload (P bytes, the same for every frame) behind the
+        holes; the checksum and ``head_fn(P)`` then cover the protected bytes.  None when a frame needs a deeper
+        format or a 64-bit length: the caller then goes frame by frame through ``lossless_encode``."""
         t, core = self.torch, self.core
         if bits not in core.DEPTHS:
             bits = 16
         nb = core._lib.load().payload_bytes(N, C, bits)
-        if n_frames == 0 or nb >= 0xFFFFFFFF:
+        plen = nb if ecc_ratio is None else core.rs_protected_bytes(nb, *ecc_ratio)
+        if n_frames == 0 or plen >= 0xFFFFFFFF:
             return None
-        stream = t.empty((n_frames, 32 + nb), dtype=t.uint8, device=self.device)
+        stream = t.empty((n_frames, 32 + plen), dtype=t.uint8, device=self.device)
         pay = stream[:, 32:]
         enc = core.analogue_batch(profile, self._up(pcm), fmt, n_frames, N, C, bits, little_endian,
-                                  raw_be_ints=raw_be_ints, out=pay)
+                                  raw_be_ints=raw_be_ints, out=None if ecc_ratio else pay)
         if enc.escalated:
             return None
-        crc = core.crc32_frames(pay, nb)
-        stream[:, :28] = t.frombuffer(bytearray(head_fn(nb)), dtype=t.uint8).to(self.device)
+        if ecc_ratio is not None:
+            core.rs_encode_frames(enc.payload, nb, *ecc_ratio, out=pay)
+        crc = core.crc32_frames(pay, plen)
+        stream[:, :28] = t.frombuffer(bytearray(head_fn(plen)), dtype=t.uint8).to(self.device)
         stream[:, 28:32] = crc.view(t.uint8).view(n_frames, 4).flip(1)       # big-endian, as int.to_bytes(4, "big")
         return self._down_bytes(stream)
 
@@ -253,6 +258,31 @@ class HipBridge:
         outs = [host[out_off[i]:out_off[i + 1]] for i in range(n)]
         del dev
         return (outs, crcs) if crc32 else outs
+
+    def rs_encode_crc16(self, payloads: list, dsize: int, codesize: int):
+        """ecc.encode of every payload and common.crc16_ansi of every protected payload (the compact-profile ECC header's
+        checksum), both on the device: one upload, ``frad_rs_encode`` and ``frad_crc16_ansi_frames``, one download of the
+        protected bytes with the checksums behind them.  -> (outputs, crcs)"""
+        t, core = self.torch, self.core
+        lib = core._lib.load()
+        n = len(payloads)
+        if n == 0:
+            return [], []
+        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, False)
+        nout = int(out_off[-1])
+        head = (nout + 15) // 16 * 16
+        out = t.empty(head + 2 * n, dtype=t.uint8, device=self.device)          # protected bytes | uint16 checksums
+        n1 = n + 1
+        off_dev = dev[ptrs[3] - ptrs[0]:ptrs[3] - ptrs[0] + 8 * n1].view(t.int64)   # out_off, uploaded with the payloads
+        stream = int(t.cuda.current_stream(self.device).cuda_stream)
+        with t.cuda.device(self.device):
+            lib.rs_encode(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), stream)
+            crc = core.crc16_ansi_frames(out[:nout], off_dev)
+            out[head:].view(t.int16).copy_(crc)
+        host = self._down_bytes(out)
+        crcs = np.frombuffer(host, np.uint16, n, head).tolist()
+        del dev
+        return [host[out_off[i]:out_off[i + 1]] for i in range(n)], crcs
 
     def rs_repair(self, payloads: list, dsize: int, codesize: int):
         """ecc.decode(p, dsize, codesize, repair=True) of every payload (tools/ecc.py:14-25) on the device.

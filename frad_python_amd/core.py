@@ -212,6 +212,60 @@ def crc32_frames(payload: torch.Tensor, nbytes: int) -> torch.Tensor:
     return out
 
 
+def rs_protected_bytes(nbytes: int, dsize: int, codesize: int) -> int:
+    """length of ecc.encode of an ``nbytes`` payload: every dsize-byte chunk (the last may be shorter) gains codesize bytes"""
+    return nbytes + -(-nbytes // dsize) * codesize
+
+
+def _require_rs_ratio(dsize: int, codesize: int):
+    if not (dsize >= 1 and codesize >= 0 and dsize + codesize <= 255):
+        raise ValueError(f"Reed-Solomon ratio ({dsize}, {codesize}) outside 1 <= dsize, 0 <= codesize, dsize + codesize <= 255")
+
+
+def _require_rows(t: torch.Tensor, width: int, what: str):
+    _require_cuda_any(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < width or (t.shape[0] > 1 and t.stride(0) < width):
+        raise ValueError(f"{what} must be a uint8 [n_frames, >= {width}] tensor with unit column stride and rows >= {width} bytes apart")
+
+
+def rs_encode_frames(payload: torch.Tensor, nbytes: int, dsize: int, codesize: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ecc.encode(payload[i, :nbytes], dsize, codesize) for every row (tools/ecc.py:6-12) into ``out[i, :P]``, P =
+    ``rs_protected_bytes(nbytes, ...)``; ``out`` may be a strided view (e.g. the payload columns of a stream with header
+    holes) and nothing else of it is written.  -> out[:, :P]"""
+    _require_rs_ratio(dsize, codesize)
+    if nbytes < 0:
+        raise ValueError("nbytes must be >= 0")
+    _require_rows(payload, nbytes, "payload")
+    P = rs_protected_bytes(nbytes, dsize, codesize)
+    if out is None:
+        out = torch.empty((payload.shape[0], _align16(P)), dtype=torch.uint8, device=payload.device)
+    _require_rows(out, P, "out")
+    if out.shape[0] != payload.shape[0] or out.device != payload.device:
+        raise ValueError(f"out must hold {payload.shape[0]} rows on {payload.device}")
+    with torch.cuda.device(payload.device):
+        _lib.load().rs_encode_frames(payload.data_ptr(), payload.stride(0), payload.shape[0], nbytes, dsize, codesize,
+                                     out.data_ptr(), out.stride(0), _stream_ptr())
+    return out[:, :P]
+
+
+def crc16_ansi_frames(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """common.crc16_ansi of ``data[offsets[i]:offsets[i + 1]]`` for every frame, as int16 bit patterns on the device (the
+    checksum a compact-profile ECC header stores, tools/asfh.py).  The offsets are checked against ``data`` before the launch
+    (one small device-to-host read)."""
+    _require_cuda(data, "data"); _require_cuda(offsets, "offsets")
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("data must be a 1-D uint8 tensor")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or offsets.device != data.device:
+        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries on the device of data")
+    n = offsets.numel() - 1
+    if n and not bool(((offsets[1:] >= offsets[:-1]).all() & (offsets[0] >= 0) & (offsets[-1] <= data.numel())).item()):
+        raise ValueError("offsets must be non-decreasing and within data")
+    out = torch.empty(n, dtype=torch.int16, device=data.device)
+    with torch.cuda.device(data.device):
+        _lib.load().crc16_ansi_frames(data.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), _stream_ptr())
+    return out
+
+
 def _pcm_out_tensor(fmt: str, shape, device) -> torch.Tensor:
     """uint8 storage for `shape` elements of PCM format `fmt` (torch has no big-endian or unsigned 16/32/64 dtypes)"""
     n = 1

@@ -282,6 +282,108 @@ __global__ void __launch_bounds__(64) k_rs_fix(const unsigned char* __restrict__
     }
 }
 
+// ---- fixed-stride encode (frad_rs_encode_frames): n_frames payloads of the same length, frame f at in + f * in_stride, its
+// protected form at out + f * out_stride.  Every frame has the same block count, so the work splits into units of 64
+// consecutive blocks of one frame with no offset arrays.  One wave per unit, four waves per workgroup sharing one table:
+//   stage-in:  the unit's input range (contiguous) with 4-byte loads into LDS, one row per block (row pitch an odd number of
+//              dwords: the lanes' dword reads of their own rows hit 64 different banks);
+//   LFSR:      one lane per block, the register file in VGPRs as WM dwords with the codesize bytes at the top (bytes below
+//              4 WM - cs stay zero), one table row per data byte: prod[fb] = fb * g packed like the register, read as WM / 2
+//              ds_read_b64, and the shift is a byte funnel across dwords -- WM / 2 LDS reads per data byte instead of cs
+//              exp-table lookups;
+//   stage-out: the check bytes go to a second LDS row per block and the unit's output range (contiguous) leaves as
+//              data || check per block with 4-byte stores; bytes outside a frame's P output bytes are never written.
+// When dsize, codesize and nbytes are multiples of 4 (`wide`, e.g. (96, 24) on 2048 x 2 x 32-bit payloads) no dword of the
+// input or output range straddles two LDS rows, so both stages move dwords instead of bytes.
+constexpr int RSF_WAVES = 4;
+
+__device__ __forceinline__ uint32_t rsf_bswap(uint32_t x) {
+    return (x >> 24) | ((x >> 8) & 0xff00u) | ((x << 8) & 0xff0000u) | (x << 24);
+}
+
+template <int WM>
+__global__ void __launch_bounds__(256) k_rs_frames(const unsigned char* __restrict__ in, long long in_stride, long long n_frames,
+                                                   long long nbytes, int dsize, int cs, const uint32_t* __restrict__ prod,
+                                                   unsigned char* __restrict__ out, long long out_stride, long long nblk, long long upf,
+                                                   int dpitch, int cpitch, int aligned_in, int aligned_out, int wide) {
+    FRAD_DYN_SMEM(smem);
+    uint32_t* tab = reinterpret_cast<uint32_t*>(smem);                      // [256][WM]
+    for (int i = threadIdx.x; i < 256 * WM; i += blockDim.x) tab[i] = prod[i];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned char* sd = smem + 256 * WM * 4 + wave * 64 * (dpitch + cpitch);   // [64][dpitch] data rows
+    unsigned char* sc = sd + 64 * dpitch;                                       // [64][cpitch] check rows
+    const int bout = dsize + cs;
+    const long long units = n_frames * upf;
+    for (long long u = (long long)blockIdx.x * RSF_WAVES + wave; u < units; u += (long long)gridDim.x * RSF_WAVES) {
+        const long long f = u / upf, k0 = (u - f * upf) * 64;
+        const int nk = nblk - k0 < 64 ? (int)(nblk - k0) : 64;
+        const long long left = nbytes - k0 * dsize;
+        const int len_in = left < 64ll * dsize ? (int)left : 64 * dsize;
+        const int m_last = len_in - (nk - 1) * dsize;                           // data bytes of the unit's last block
+        const int len_out = len_in + nk * cs;
+        const unsigned char* src = in + f * in_stride + k0 * dsize;             // k0 * dsize: a multiple of 64
+        unsigned char* dst = out + f * out_stride + k0 * bout;
+        for (int q = lane * 4; q < len_in; q += 256) {
+            uint32_t w = 0;
+            if (aligned_in && q + 4 <= len_in) w = *reinterpret_cast<const uint32_t*>(src + q);
+            else for (int i = 0; i < 4 && q + i < len_in; ++i) w |= (uint32_t)src[q + i] << (8 * i);
+            int b = q / dsize, r = q - b * dsize;
+            if (wide) { *reinterpret_cast<uint32_t*>(sd + b * dpitch + r) = w; continue; }   // a dword never straddles two rows
+            for (int i = 0; i < 4 && q + i < len_in; ++i) {
+                sd[b * dpitch + r] = (unsigned char)(w >> (8 * i));
+                if (++r == dsize) { r = 0; ++b; }
+            }
+        }
+        team_sync<64>();
+        if (lane < nk) {
+            const int m = lane == nk - 1 ? m_last : dsize;
+            const unsigned char* d = sd + lane * dpitch;
+            uint32_t st[WM];
+#pragma unroll
+            for (int w = 0; w < WM; ++w) st[w] = 0u;
+            auto step = [&](uint32_t c) {
+                const uint32_t fb = (c ^ (st[WM - 1] >> 24)) & 0xffu;
+                const v2u* row = reinterpret_cast<const v2u*>(tab + fb * WM);
+#pragma unroll
+                for (int h = WM / 2 - 1; h >= 0; --h) {
+                    const v2u p = row[h];
+                    const uint32_t below = h ? st[2 * h - 1] : 0u;
+                    st[2 * h + 1] = ((st[2 * h + 1] << 8) | (st[2 * h] >> 24)) ^ p[1];
+                    st[2 * h] = ((st[2 * h] << 8) | (below >> 24)) ^ p[0];
+                }
+            };
+            int k = 0;
+            for (; k + 4 <= m; k += 4) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(d + k);
+                step(w); step(w >> 8); step(w >> 16); step(w >> 24);
+            }
+            for (; k < m; ++k) step(d[k]);
+            uint32_t* c = reinterpret_cast<uint32_t*>(sc + lane * cpitch);    // check byte i = register byte 4 WM - 1 - i
+#pragma unroll
+            for (int w = 0; w < WM; ++w) c[WM - 1 - w] = rsf_bswap(st[w]);
+        }
+        team_sync<64>();
+        for (int q = lane * 4; q < len_out; q += 256) {
+            int b = q / bout, r = q - b * bout;
+            uint32_t w = 0;
+            const int n4 = len_out - q < 4 ? len_out - q : 4;
+            if (wide) {                                                     // the dword lies in one data or one check row
+                const int mb = b == nk - 1 ? m_last : dsize;
+                w = r < mb ? *reinterpret_cast<const uint32_t*>(sd + b * dpitch + r) : *reinterpret_cast<const uint32_t*>(sc + b * cpitch + (r - mb));
+            } else for (int i = 0; i < n4; ++i) {
+                const int mb = b == nk - 1 ? m_last : dsize;
+                const uint32_t v = r < mb ? sd[b * dpitch + r] : sc[b * cpitch + (r - mb)];
+                w |= v << (8 * i);
+                if (++r == mb + cs) { r = 0; ++b; }
+            }
+            if (aligned_out && n4 == 4) *reinterpret_cast<uint32_t*>(dst + q) = w;
+            else for (int i = 0; i < n4; ++i) dst[q + i] = (unsigned char)(w >> (8 * i));
+        }
+        team_sync<64>();
+    }
+}
+
 namespace {
 
 std::mutex g_mu;
@@ -353,13 +455,83 @@ int rs_check_args(const void* in, const int64_t* in_off, const int64_t* blk_off,
     return FRAD_OK;
 }
 
+
+std::map<std::pair<int, int>, uint32_t*> g_prod;          // (device, codesize) -> fb * g rows of k_rs_frames
+
+// register width of k_rs_frames for a codesize: an even number of dwords, from a short list of instantiations
+int rsf_width(int cs) {
+    static const int widths[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
+    const int need = (cs + 3) / 4;
+    for (int w : widths) if (w >= need) return w;
+    return 64;
+}
+
+int get_rs_prod(int cs, const uint32_t** out) {
+    int dev = 0; ECHK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_prod.find({dev, cs});
+    if (it != g_prod.end()) { *out = it->second; return FRAD_OK; }
+    unsigned char ex[512], lg[256] = {0};
+    unsigned x = 1;
+    for (int i = 0; i < 255; ++i) {
+        ex[i] = ex[i + 255] = (unsigned char)x;
+        lg[x] = (unsigned char)i;
+        x <<= 1;
+        if (x & 0x100u) x ^= 0x11du;
+    }
+    auto mul = [&](unsigned a, unsigned b) -> unsigned { return (a && b) ? ex[lg[a] + lg[b]] : 0u; };
+    std::vector<unsigned> gpoly(cs + 1, 0);
+    gpoly[0] = 1;
+    for (int i = 0; i < cs; ++i) {
+        const unsigned a = ex[i];
+        for (int j = i + 1; j >= 1; --j) gpoly[j] = gpoly[j - 1] ^ mul(gpoly[j], a);
+        gpoly[0] = mul(gpoly[0], a);
+    }
+    const int WM = rsf_width(cs), pad = 4 * WM - cs;
+    std::vector<uint32_t> h((size_t)256 * WM, 0u);
+    for (int fb = 0; fb < 256; ++fb)
+        for (int j = 0; j < cs; ++j) {                     // register byte pad + j holds r_j
+            const int a = pad + j;
+            h[(size_t)fb * WM + a / 4] |= mul(fb, gpoly[j]) << (8 * (a & 3));
+        }
+    uint32_t* d = nullptr;
+    ECHK(hipMalloc(&d, h.size() * 4));
+    ECHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    g_prod[{dev, cs}] = d; *out = d;
+    return FRAD_OK;
+}
+
+template <int WM>
+int rsf_launch(const unsigned char* in, long long in_stride, long long n_frames, long long nbytes, int dsize, int cs,
+               unsigned char* out, long long out_stride, hipStream_t s) {
+    const uint32_t* prod = nullptr;
+    const int rc = get_rs_prod(cs, &prod);
+    if (rc != FRAD_OK) return rc;
+    const long long nblk = (nbytes + dsize - 1) / dsize, upf = (nblk + 63) / 64;
+    const int dw = (dsize + 3) / 4, dpitch = 4 * (dw | 1), cpitch = 4 * (WM + 1);
+    const size_t lds = (size_t)256 * WM * 4 + (size_t)RSF_WAVES * 64 * (dpitch + cpitch);
+    const int aligned_in = ((reinterpret_cast<uintptr_t>(in) | (uintptr_t)in_stride) & 3u) == 0;
+    const int aligned_out = ((reinterpret_cast<uintptr_t>(out) | (uintptr_t)out_stride) & 3u) == 0;
+    const int wide = dsize % 4 == 0 && cs % 4 == 0 && nbytes % 4 == 0;     // rows and their boundaries are dword-aligned
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    const long long want = (n_frames * upf + RSF_WAVES - 1) / RSF_WAVES, cap = 8ll * cus;
+    allow_lds(k_rs_frames<WM>, lds);
+    hipLaunchKernelGGL(k_rs_frames<WM>, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * RSF_WAVES), lds, s, in, in_stride,
+                       n_frames, nbytes, dsize, cs, prod, out, out_stride, nblk, upf, dpitch, cpitch, aligned_in, aligned_out, wide);
+    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    return FRAD_OK;
+}
+
 }  // namespace
 
 int ecc_last_hip_error() { return g_last; }
 void ecc_clear() {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_tab) (void)hipFree(kv.second);
+    for (auto& kv : g_prod) (void)hipFree(kv.second);
     g_tab.clear();
+    g_prod.clear();
 }
 
 }  // namespace frad
@@ -399,4 +571,31 @@ extern "C" int frad_rs_repair(const void* in, const int64_t* in_off, const int64
                        static_cast<const int32_t*>(work), corrected, failed);
     if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
     return FRAD_OK;
+}
+
+extern "C" int frad_rs_encode_frames(const void* in, int64_t in_stride, int64_t n_frames, int64_t nbytes, int32_t dsize,
+                                     int32_t codesize, void* out, int64_t out_stride, void* stream) {
+    using namespace frad;
+    if (dsize < 1 || codesize < 0 || dsize + codesize > 255 || n_frames < 0 || nbytes < 0) return FRAD_E_INVALID;
+    const long long nblk = (nbytes + dsize - 1) / dsize, plen = nbytes + nblk * codesize;
+    if (n_frames > 1 && (in_stride < nbytes || out_stride < plen)) return FRAD_E_INVALID;
+    if (n_frames == 0 || nbytes == 0) return FRAD_OK;
+    if (!in || !out) return FRAD_E_INVALID;
+    const auto* i8 = static_cast<const unsigned char*>(in);
+    auto* o8 = static_cast<unsigned char*>(out);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (rsf_width(codesize)) {
+        case 2: return rsf_launch<2>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 4: return rsf_launch<4>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 6: return rsf_launch<6>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 8: return rsf_launch<8>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 10: return rsf_launch<10>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 12: return rsf_launch<12>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 16: return rsf_launch<16>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 20: return rsf_launch<20>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 24: return rsf_launch<24>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 32: return rsf_launch<32>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        case 48: return rsf_launch<48>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+        default: return rsf_launch<64>(i8, in_stride, n_frames, nbytes, dsize, codesize, o8, out_stride, s);
+    }
 }

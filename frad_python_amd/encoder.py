@@ -52,9 +52,11 @@ class EncodeResult:
 
 class Encoder:
     def __init__(self, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *, bridge=None,
-                 allow_profile2: bool = False):
+                 allow_profile2: bool = False, allow_ecc: bool = False):
         # profile 2 (TNS) is outside the reference's AVAILABLE list; `allow_profile2=True` admits it on this instance only
         self.allow_profile2 = bool(allow_profile2)
+        # `allow_ecc=True` makes set_ecc the reference's: Reed-Solomon protection of every frame, on the device
+        self.allow_ecc = bool(allow_ecc)
         if profile not in AVAILABLE and not (profile == 2 and self.allow_profile2):
             print(f"Invalid profile! Available: {AVAILABLE}", file=sys.stderr)
             sys.exit(1)
@@ -78,13 +80,32 @@ class Encoder:
         return self._bridge
 
     # ------------------------------------------------------------------ framing helpers
-    def _emit(self, frad: bytes, depth_idx: int, fsize: int) -> bytes:
-        if self.asfh.ecc:
-            raise NotImplementedError("Reed-Solomon ECC is host-side and not part of the MI355X transform core")
+    def _head(self, depth_idx: int, fsize: int) -> ASFH:
         a = self.asfh
         a.bit_depth_index, a.channels, a.fsize = depth_idx, self.channels, fsize
         a.srate = compact.get_valid_srate(self.srate) if a.profile in profiles.COMPACT else self.srate
-        return a.write(frad)
+        return a
+
+    def _emit(self, frad: bytes, depth_idx: int, fsize: int) -> bytes:
+        if self.asfh.ecc and not self.allow_ecc:
+            raise NotImplementedError("Reed-Solomon ECC is off unless the Encoder is built with allow_ecc=True")
+        return self._head(depth_idx, fsize).write(frad)
+
+    def _emit_all(self, items: list) -> list:
+        """(payload, depth index, fsize) of a batch's frames -> the frames.  With ECC (encoder.py:102) every payload is
+        protected and its header checksum computed on the device in one batch: crc32 for the lossless profiles, crc16_ansi
+        for the compact ones; the host only writes the headers."""
+        if not self.asfh.ecc or not items:
+            return [self._emit(*it) for it in items]
+        if not self.allow_ecc:
+            raise NotImplementedError("Reed-Solomon ECC is off unless the Encoder is built with allow_ecc=True")
+        dsize, cs = self.asfh.ecc_dsize, self.asfh.ecc_codesize
+        payloads = [it[0] for it in items]
+        if self.asfh.profile in profiles.COMPACT:
+            prot, crcs = self.bridge.rs_encode_crc16(payloads, dsize, cs)
+        else:
+            prot, crcs = self.bridge.rs_encode(payloads, dsize, cs, crc32=True)
+        return [self._head(idx, fsize).write(p, crc=c) for (_, idx, fsize), p, c in zip(items, prot, crcs)]
 
     @staticmethod
     def _deflate(body: bytes) -> bytes:
@@ -101,28 +122,27 @@ class Encoder:
             # DCT, masking, TNS analysis, quantiser and the three Golomb streams on the device; the host deflates and frames
             bodies = self.bridge.p2_encode_bodies(pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate),
                                                   self.loss_level, hop, n_valid)
-            for frad in _map_zlib(self._deflate, bodies):
-                out.append(self._emit(frad, _P2_DEPTHS.index(bits), n_valid))
+            out += self._emit_all([(frad, _P2_DEPTHS.index(bits), n_valid) for frad in _map_zlib(self._deflate, bodies)])
         elif prof == 1:
             bits = self.bit_depth if self.bit_depth in _P1_DEPTHS else 16
             N = compact.get_samples_min_ge(n_eff)
             # quantiser and Exp-Golomb-Rice coder behind the bridge (on the device); the host only deflates (profile1.py:50) and frames
             bodies = self.bridge.p1_encode_bodies(pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate),
                                                   self.loss_level, hop, n_valid)
-            for frad in _map_zlib(self._deflate, bodies):
-                out.append(self._emit(frad, _P1_DEPTHS.index(bits), n_valid))
+            out += self._emit_all([(frad, _P1_DEPTHS.index(bits), n_valid) for frad in _map_zlib(self._deflate, bodies)])
         else:
             bits = self.bit_depth if self.bit_depth in _LOSSLESS_DEPTHS else 16
             whole = getattr(self.bridge, "lossless_encode_stream", None)
-            if whole is not None and not self.asfh.ecc and n_frames > 1:
-                # headers and checksums on the device, one copy back (bridge.py); falls through when a frame escalates
+            if whole is not None and n_frames > 1 and (not self.asfh.ecc or self.allow_ecc):
+                # headers, Reed-Solomon and checksums on the device, one copy back (bridge.py); falls through when a frame escalates
                 a = self.asfh
                 a.bit_depth_index, a.channels, a.fsize, a.srate = _LOSSLESS_DEPTHS.index(bits), C, n_eff, self.srate
-                got = whole(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, a.endian, a.lossless_head)
+                ecc_kw = {"ecc_ratio": (a.ecc_dsize, a.ecc_codesize)} if a.ecc else {}
+                got = whole(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, a.endian, a.lossless_head, **ecc_kw)
                 if got is not None:
                     return got
-            for frad, used in self.bridge.lossless_encode(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, self.asfh.endian):
-                out.append(self._emit(frad, _LOSSLESS_DEPTHS.index(used), n_eff))
+            out += self._emit_all([(frad, _LOSSLESS_DEPTHS.index(used), n_eff) for frad, used in
+                                   self.bridge.lossless_encode(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, self.asfh.endian)])
         return b"".join(out)
 
     def inner(self, stream: bytes, flush: bool) -> EncodeResult:
@@ -255,7 +275,19 @@ class Encoder:
         self.bit_depth = bit_depth
 
     def set_ecc(self, ecc: bool, ecc_ratio):
-        # protected streams come from Repairer(ecc_ratio).process(stream), which writes the bytes set_ecc(True, ...) would
+        if self.allow_ecc:                                   # encoder.py:201-209
+            self.asfh.ecc = bool(ecc)
+            dsize_zero, exceed_255 = ecc_ratio[0] == 0, ecc_ratio[0] + ecc_ratio[1] > 255
+            if dsize_zero or exceed_255:
+                if dsize_zero:
+                    print("ECC data size must not be zero", file=sys.stderr)
+                if exceed_255:
+                    print(f"ECC data size and check size must not exceed 255, given: {ecc_ratio[0]} and {ecc_ratio[1]}", file=sys.stderr)
+                print("Setting ECC to default 96 24", file=sys.stderr)
+                ecc_ratio = (96, 24)
+            self.asfh.ecc_dsize, self.asfh.ecc_codesize = ecc_ratio
+            return
+        # without the opt-in, protected streams come from Repairer(ecc_ratio).process(stream), which writes the same bytes
         if ecc:
             raise NotImplementedError("Encoder-side ECC is not built: protect the stream with "
                                       "frad_python_amd.Repairer(ecc_ratio).process(stream), which writes the same bytes")

@@ -69,16 +69,18 @@ class ASFH:
         """The 28 header bytes of a lossless frame that do not depend on its payload (the CRC-32 follows)."""
         return self._prefix(length) + _LOSSLESS_TAIL.pack(self.channels - 1, self.ecc_dsize, self.ecc_codesize, self.srate, self.fsize)
 
-    def write(self, frad: bytes) -> bytes:
+    def write(self, frad: bytes, crc: int | None = None) -> bytes:
+        """``crc``: the header's checksum of ``frad`` when it is already known (crc16_ansi for a compact ECC frame, crc32
+        otherwise), e.g. computed on the device with the payload; None computes it here."""
         parts = [self._prefix(len(frad))]
         if self.profile in COMPACT:
             parts.append(encode_css_prf1(self.channels, self.srate, self.fsize, False))
             parts.append(bytes([max(self.overlap_ratio - 1, 0)]))
             if self.ecc:
-                parts.append(bytes([self.ecc_dsize, self.ecc_codesize]) + crc16_ansi(frad).to_bytes(2, "big"))
+                parts.append(bytes([self.ecc_dsize, self.ecc_codesize]) + (crc16_ansi(frad) if crc is None else crc).to_bytes(2, "big"))
         else:
             parts.append(_LOSSLESS_TAIL.pack(self.channels - 1, self.ecc_dsize, self.ecc_codesize, self.srate, self.fsize))
-            parts.append(crc32(frad).to_bytes(4, "big"))
+            parts.append((crc32(frad) if crc is None else crc).to_bytes(4, "big"))
         parts.append(frad)
         return b"".join(parts)
 

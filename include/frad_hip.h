@@ -262,6 +262,18 @@ int frad_rs_encode(const void* in, const int64_t* in_off, const int64_t* blk_off
 int frad_rs_repair(const void* in, const int64_t* in_off, const int64_t* blk_off, const int64_t* out_off, int64_t n_frames,
                    int64_t n_blocks, int32_t dsize, int32_t codesize, void* out, int32_t* corrected, int32_t* failed,
                    int32_t* work, void* stream);
+/* frad_rs_encode_frames == frad_rs_encode of n_frames payloads of the same length `nbytes` (the lossless profiles' batches),
+ * without offset arrays: frame f is read from in + f * in_stride and ecc.encode of it, P = nbytes + ceil(nbytes / dsize) *
+ * codesize bytes, is written to out + f * out_stride.  Only those P bytes of each output row are written, so the row may
+ * start behind a frame header and the gaps between rows stay untouched.  Same code as frad_rs_encode; in and out are
+ * device memory of any alignment and must not overlap; with n_frames > 1, in_stride >= nbytes and out_stride >= P.
+ * 1 <= dsize, 0 <= codesize, dsize + codesize <= 255.
+ * frad_crc16_ansi_frames: crc_out[f] = common.crc16_ansi (reflected polynomial 0xA001, initial value 0, no final XOR) of
+ * data[offsets[f] .. offsets[f+1]), the checksum a compact-profile ECC header stores (tools/asfh.py).  offsets is a DEVICE
+ * int64 array of n_frames + 1 non-decreasing entries, crc_out device uint16 [n_frames]; any alignment. */
+int frad_rs_encode_frames(const void* in, int64_t in_stride, int64_t n_frames, int64_t nbytes, int32_t dsize, int32_t codesize,
+                          void* out, int64_t out_stride, void* stream);
+int frad_crc16_ansi_frames(const void* data, const int64_t* offsets, int64_t n_frames, uint16_t* crc_out, void* stream);
 
 /* ---- decoder output conversion (R1 epilogue) and native frame-header scan (row 8f #1) ------------------------------
  * frad_from_f64 == backend.pcmformat.from_f64 followed by .astype(fmt) as the reference's caller applies it to every
