@@ -63,6 +63,7 @@ SYMBOLS = {
                                c_void_p, c_void_p, c_void_p]),
     "frad_rs_encode_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "frad_crc16_ansi_frames": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frad_inflate_raw": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "frad_bench_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
@@ -228,6 +229,9 @@ class FradLib:
 
     def crc16_ansi_frames(self, data, offsets, n_frames, out, stream=0):
         self._check(self.dll.frad_crc16_ansi_frames(data, offsets, n_frames, out, stream))
+
+    def inflate_raw(self, src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream=0):
+        self._check(self.dll.frad_inflate_raw(src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream))
 
     def bench_copy(self, src, dst, nbytes, stream=0):
         self._check(self.dll.frad_bench_copy(src, dst, nbytes, stream))

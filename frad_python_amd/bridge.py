@@ -205,6 +205,64 @@ class HipBridge:
             pcm = out.cpu().numpy().reshape(-1, C)
         return pcm, nxt.cpu().numpy()
 
+    # ------------------------------------------------------------------ device inflate (Decoder(device_inflate=True))
+    def inflate_run(self, payloads: list, profile: int, N, C):
+        """The deflated payloads of a compact run -> their inflated bodies on the device, compacted: (bodies uint8 with the 8
+        bytes of tail slack frad_p{1,2}_golomb_decode read, offsets int64 [n + 1]), or None when any frame does not inflate
+        (status != 0): the caller then takes the whole run through the host's zlib.  One upload of the payloads, one
+        download of two numbers."""
+        t, core = self.torch, self.core
+        lib = core._lib.load()
+        n = len(payloads)
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(p) for p in payloads], out=off[1:])
+        src = self._up(b"".join(payloads))
+        stride = lib.p1_golomb_bound(N, C) if profile == 1 else lib.p2_golomb_bound(N, C)     # multiples of 16
+        rows, nbytes, status = core.inflate_batch(src, t.from_numpy(off).to(self.device), stride)
+        offsets = t.empty(n + 1, dtype=t.int64, device=self.device)
+        with t.cuda.device(self.device):
+            lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, 0, offsets.data_ptr(), core._stream_ptr())
+            bad, total = t.stack([(status != 0).any().to(t.int64), offsets[-1]]).tolist()
+            if bad:
+                return None
+            bodies = t.zeros(total + 8, dtype=t.uint8, device=self.device)
+            if total:
+                lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, bodies.data_ptr(), offsets.data_ptr(), core._stream_ptr())
+        return bodies, offsets
+
+    def _frames_dev(self, profile, bodies, offsets, N, C, bits, srate):
+        """inflated bodies on the device -> float64 frames [n, N, C] on the device (Golomb decode, K8 / p2 synthesis)"""
+        if profile == 1:
+            q, tq, _ = self.core.p1_golomb_decode_batch(bodies, offsets, N, C)
+            return self.core.p1_digital_batch(q, tq, N, C, bits, srate)
+        q, tq, lpc, _ = self.core.p2_golomb_decode_batch(bodies, offsets, N, C)
+        return self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate)
+
+    def decode_bodies_deflated(self, profile, payloads: list, N, C, bits, srate):
+        """``p{1,2}_decode_bodies`` from the deflated payloads, inflated on the device; None when a frame does not inflate."""
+        got = self.inflate_run(payloads, profile, N, C)
+        if got is None:
+            return None
+        return self._frames_dev(profile, *got, N, C, bits, srate).cpu().numpy()
+
+    def decode_run_deflated(self, profile, payloads: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
+        """``p{1,2}_decode_run`` from the deflated payloads: inflate, Golomb decode, K8 / p2 synthesis, the cross-fade and the
+        optional output conversion, all on the device -> (PCM [n * cut, C], new tail float64); None when a frame does not
+        inflate."""
+        from .backend.pcmformat import ff_format_to_numpy_type
+        t = self.torch
+        got = self.inflate_run(payloads, profile, N, C)
+        if got is None:
+            return None
+        frames = self._frames_dev(profile, *got, N, C, bits, srate)
+        pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
+        out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
+        if out.dtype == t.uint8:
+            pcm = np.frombuffer(out.cpu().numpy().tobytes(), ff_format_to_numpy_type(out_format)).reshape(-1, C)
+        else:
+            pcm = out.cpu().numpy().reshape(-1, C)
+        return pcm, nxt.cpu().numpy()
+
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch
         return self.core.p1_digital_batch(t.from_numpy(np.ascontiguousarray(q, np.int32)).to(self.device),

@@ -532,3 +532,45 @@ def p1_overlap_add(frames: torch.Tensor, overlap_ratio: int, prev_tail: torch.Te
             out = torch.empty((n_frames, cut, C), dtype=torch.float64, device=frames.device)
             _lib.load().p1_overlap_add(frames.data_ptr(), n_frames, N, C, overlap_ratio, pt, out.data_ptr(), nxt.data_ptr(), _stream_ptr())
     return out, nxt
+
+
+# ---------------------------------------------------------------------------------------------
+# raw DEFLATE inflate (frad_inflate_raw): the zlib.decompress(frad, wbits=-15) of profile1.py:59 / profile2.py:61-64
+# ---------------------------------------------------------------------------------------------
+INFLATE_OK, INFLATE_INVALID, INFLATE_OVERFLOW = 0, 1, 2
+
+
+def inflate_batch(src: torch.Tensor, offsets: torch.Tensor, dst_stride: int):
+    """Raw DEFLATE decode of a batch of independent streams on the device (RFC 1951, no wrapper, no dictionary).
+
+    ``src`` uint8 [total], ``offsets`` int64 [n_frames + 1] (both CUDA tensors): stream i is ``src[offsets[i]:offsets[i+1]]``.
+    Returns ``(dst uint8 [n_frames, dst_stride], dst_bytes int64 [n_frames], status int32 [n_frames])``: with status 0 row i's
+    first ``dst_bytes[i]`` bytes equal ``zlib.decompress(stream_i, wbits=-15)``; status 1 = zlib rejects the stream, 2 = the
+    output would exceed ``dst_stride`` bytes.  ``dst_stride`` a positive multiple of 16.  The offsets are checked against
+    ``src`` here (one device-to-host read), so no caller buffer reaches the kernel unchecked."""
+    _require_cuda(src, "src"); _require_cuda(offsets, "offsets")
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError(f"src must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries")
+    if offsets.device != src.device:
+        raise ValueError("src and offsets must be on the same device")
+    dst_stride = int(dst_stride)
+    if dst_stride < 16 or dst_stride % 16:
+        raise ValueError(f"dst_stride must be a positive multiple of 16, got {dst_stride}")
+    n_frames = offsets.numel() - 1
+    if n_frames > 0x7fffffff:
+        raise ValueError("at most 2^31 - 1 streams per batch")
+    lo, hi, mono = torch.stack([offsets.min(), offsets.max(), (offsets[1:] < offsets[:-1]).any().to(torch.int64)]).tolist()
+    if lo < 0 or hi > src.numel() or mono:
+        raise ValueError(f"offsets must be non-decreasing and within [0, {src.numel()}] (got min {lo}, max {hi})")
+    # + 16 bytes behind the last row: frad_rows_compact reads a row as aligned words, one word beyond its bytes
+    dst = torch.empty(n_frames * dst_stride + 16, dtype=torch.uint8, device=src.device)
+    nbytes = torch.empty(max(n_frames, 1), dtype=torch.int64, device=src.device)
+    status = torch.empty(max(n_frames, 1), dtype=torch.int32, device=src.device)
+    if n_frames:
+        base = src.data_ptr() if src.numel() else dst.data_ptr()   # (every stream empty: nothing is read)
+        with torch.cuda.device(src.device):
+            _lib.load().inflate_raw(base, offsets.data_ptr(), n_frames, dst.data_ptr(), dst_stride, nbytes.data_ptr(),
+                                    status.data_ptr(), _stream_ptr())
+    return dst[:n_frames * dst_stride].view(n_frames, dst_stride), nbytes[:n_frames], status[:n_frames]

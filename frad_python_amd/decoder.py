@@ -60,12 +60,15 @@ class _Damaged:
 
 
 class Decoder:
-    def __init__(self, fix_error: bool = False, *, bridge=None, out_format: str | None = None):
+    def __init__(self, fix_error: bool = False, *, bridge=None, out_format: str | None = None, device_inflate: bool = False):
         """``fix_error``: ECC frames whose stored checksum does not match are repaired (Reed-Solomon, on the device) before
         they are decoded; a block that cannot be corrected becomes zero bytes (decoder.py:63-68, tools/ecc.py:14-25).
         ``out_format`` (extension): a PCM format name; DecodeResult.pcm then holds ``from_f64(pcm, fmt).astype(fmt)``
         -- what the reference's caller computes right after every process() (src/decoder.py:23) -- done on the device
-        for the bulk path, so that 2-8 bytes per sample cross PCIe instead of 8."""
+        for the bulk path, so that 2-8 bytes per sample cross PCIe instead of 8.
+        ``device_inflate`` (extension, opt-in): a run of profile-1 / profile-2 frames is inflated on the device
+        (frad_inflate_raw) and decoded there from the deflated payloads on, so the inflated bodies never visit the host; a
+        run with a frame that does not inflate there is decoded by the host-inflate path as a whole."""
         self.out_format = out_format
         self.asfh = ASFH()
         self.info = ASFH()
@@ -76,6 +79,7 @@ class Decoder:
         self.fix_error = fix_error
         self.broken_frame = False
         self._bridge = bridge
+        self.device_inflate = device_inflate
 
     @property
     def bridge(self):
@@ -117,6 +121,10 @@ class Decoder:
                         return self._overlap_host(pcm, key)
                     return [pcm.reshape(-1, channels)]             # one piece: no per-frame list, no concatenate
         payloads = [e[0] if e[0] is not None else self._data[e[1]:e[1] + e[2]] for e in entries]
+        if profile in _DEFLATED and self.device_inflate:
+            got = self._decode_run_device_inflate(key, payloads)
+            if got is not None:
+                return got
         if profile in _DEFLATED:
             bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth_idx]
             # inflate on the host (profile1.py:59, profile2.py:61); Golomb decode + dequantise (+ TNS) + IDCT behind the bridge
@@ -143,6 +151,27 @@ class Decoder:
                 pcm[i] = 0.0
         else:
             pcm = self.bridge.lossless_decode(profile, payloads, fsize, channels, _LOSSLESS_DEPTHS[depth_idx], endian)
+        return self._finish_run(pcm, key)
+
+    def _decode_run_device_inflate(self, key, payloads: list):
+        """device_inflate=True: the run's deflated payloads go to the device as they are (frad_inflate_raw, then the same
+        chain as the host-inflate path takes).  None when a frame does not inflate there: the caller's host path then decodes
+        the whole run, which keeps a frame zlib rejects a frame of zeros (profile1.py:59-60, profile2.py:63-64)."""
+        profile, fsize, channels, depth_idx, endian, srate, ratio = key
+        if getattr(self.bridge, "decode_run_deflated", None) is None:
+            return None                                              # a bridge without a device inflate (CPU-only tests)
+        bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth_idx]
+        L = fsize - fsize * (ratio - 1) // ratio if ratio else 0
+        if ratio != 0 and (not self.overlap_fragment.size or self.overlap_fragment.shape == (L, channels)):
+            prev = self.overlap_fragment if self.overlap_fragment.size else None
+            got = self.bridge.decode_run_deflated(profile, payloads, fsize, channels, bits, srate, ratio, prev, self.out_format)
+            if got is None:
+                return None
+            pcm, self.overlap_fragment = got
+            return [pcm]
+        pcm = self.bridge.decode_bodies_deflated(profile, payloads, fsize, channels, bits, srate)
+        if pcm is None:
+            return None
         return self._finish_run(pcm, key)
 
     def _repair(self, entries: list) -> list:

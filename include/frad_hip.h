@@ -235,6 +235,24 @@ size_t frad_p2_golomb_bound(int32_t N, int32_t C);
 int frad_p2_golomb_encode(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C,
                           void* bodies, int64_t body_stride, int64_t* body_bytes, void* stream);
 
+/* ---- raw DEFLATE inflate (row 8f #1): zlib.decompress(frad, wbits=-15) of the compact profiles (profile1.py:59,
+ * profile2.py:61-64) ------------------------------------------------------------------------------------------------------
+ * frad_inflate_raw: frame i is the raw DEFLATE stream (RFC 1951: no zlib / gzip wrapper, no preset dictionary)
+ * src[src_offsets[i] .. src_offsets[i+1]); it is inflated into dst + i*dst_stride, at most dst_stride bytes.
+ *   status[i]     0 = ok: dst_bytes[i] bytes were written and they equal zlib.decompress(stream, wbits=-15);
+ *                 1 = invalid or truncated: zlib rejects the stream (the rules of zlib's inflate, bytes after the final
+ *                     block ignored, an empty stream invalid);
+ *                 2 = the output would exceed dst_stride bytes.
+ *                 With a non-zero status dst_bytes[i] = 0 and the row's contents are unspecified (nothing is written
+ *                 outside the row).
+ * src_offsets: n_frames + 1 non-decreasing entries (DEVICE int64); the source is read bytewise and never outside
+ * [src_offsets[0], src_offsets[n_frames]), so `src` needs neither alignment nor slack.  dst 16-byte aligned, dst_stride a
+ * positive multiple of 16 (frad_p1_golomb_bound / frad_p2_golomb_bound are); dst_bytes int64 [n_frames], status int32
+ * [n_frames].  Only the bytes [0, dst_bytes[i]) of a row are written.  FRAD_E_INVALID for a NULL pointer or a stride /
+ * alignment outside these rules.  One wave per frame; LDS per wave about 6 KiB + min(dst_stride, 32 KiB). */
+int frad_inflate_raw(const void* src, const int64_t* src_offsets, int64_t n_frames, void* dst, int64_t dst_stride,
+                     int64_t* dst_bytes, int32_t* status, void* stream);
+
 /* ---- frame header checksum (row 8f #1) --------------------------------------------------------
  * crc_out[i] = zlib.crc32 of the `nbytes` payload bytes of frame i (at data + i*stride), the value
  * ASFH.write puts into a lossless frame's header (src/libfrad/tools/asfh.py:51-73), so a batch's
