@@ -64,6 +64,8 @@ SYMBOLS = {
     "frad_rs_encode_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "frad_crc16_ansi_frames": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "frad_inflate_raw": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "frad_deflate_raw": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "frad_deflate_stride": (c_int64, [c_int64]),
     "frad_bench_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
@@ -232,6 +234,14 @@ class FradLib:
 
     def inflate_raw(self, src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream=0):
         self._check(self.dll.frad_inflate_raw(src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream))
+
+    def deflate_raw(self, src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream=0):
+        self._check(self.dll.frad_deflate_raw(src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream))
+
+    def deflate_stride(self, max_body_bytes):
+        r = int(self.dll.frad_deflate_stride(max_body_bytes))
+        self._check(r if r < 0 else 0)
+        return r
 
     def bench_copy(self, src, dst, nbytes, stream=0):
         self._check(self.dll.frad_bench_copy(src, dst, nbytes, stream))

@@ -148,6 +148,57 @@ class HipBridge:
         host = self._down_bytes(flat) if flat.numel() else b""
         return [host[off[i]:off[i + 1]] for i in range(n_frames)]
 
+    # ------------------------------------------------------------------ device deflate (Encoder(device_deflate=True))
+    def deflate_payloads(self, flat, offsets) -> list:
+        """Pre-deflate bodies on the device (``flat`` uint8, frame i at ``offsets[i]:offsets[i+1]``) -> the deflated payloads,
+        ``zlib.compressobj(-1, DEFLATED, -15)`` of each body (profile1.py:50, profile2.py:54): frad_deflate_raw, the rows
+        compacted with frad_rows_compact, one copy back of the payloads with their offsets and statuses.  A body the device
+        leaves to the host (status 1: 65 274 bytes or more) is copied back alone and deflated by zlib."""
+        import zlib
+        t, core = self.torch, self.core
+        lib = core._lib.load()
+        n = offsets.numel() - 1
+        if n == 0:
+            return []
+        rows, nbytes, status = core.deflate_batch(flat, offsets)
+        stride = rows.shape[1]
+        pay_off = t.empty(n + 1, dtype=t.int64, device=self.device)
+        with t.cuda.device(self.device):
+            lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, 0, pay_off.data_ptr(), core._stream_ptr())
+            total = int(pay_off[-1].item())
+            head = (total + 7) // 8 * 8
+            out = t.empty(head + 8 * (n + 1) + 4 * n, dtype=t.uint8, device=self.device)    # payloads | offsets | statuses
+            if total:
+                lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, out.data_ptr(), pay_off.data_ptr(), core._stream_ptr())
+            out[head:head + 8 * (n + 1)].view(t.int64).copy_(pay_off)
+            out[head + 8 * (n + 1):].view(t.int32).copy_(status)
+        host = self._down_bytes(out)
+        off = np.frombuffer(host, np.int64, n + 1, head)
+        st = np.frombuffer(host, np.int32, n, head + 8 * (n + 1))
+        pays = [host[off[i]:off[i + 1]] for i in range(n)]
+        left = np.flatnonzero(st != 0)
+        if left.size:                                                 # only these bodies come back
+            boff = offsets.cpu().numpy()
+            for i in left.tolist():
+                body = self._down_bytes(flat[int(boff[i]):int(boff[i + 1])]) if boff[i + 1] > boff[i] else b""
+                co = zlib.compressobj(zlib.Z_DEFAULT_COMPRESSION, zlib.DEFLATED, -15)
+                pays[i] = co.compress(body) + co.flush()
+        self.last_deflate_host = int(left.size)
+        return pays
+
+    def p1_encode_payloads(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
+        """``p1_encode_bodies`` with the deflate on the device too: K7, the Exp-Golomb-Rice coder and zlib's raw deflate,
+        -> the deflated payload of every frame (profile1.py:15-50); the bodies stay on the device."""
+        q, tq = self.core.p1_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
+                                            frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
+        return self.deflate_payloads(*self.core.p1_golomb_encode_batch(q, tq))
+
+    def p2_encode_payloads(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
+        """``p2_encode_bodies`` with the deflate on the device too (profile2.py:15-54)."""
+        q, tq, lpc = self.core.p2_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
+                                                 frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
+        return self.deflate_payloads(*self.core.p2_golomb_encode_batch(q, tq, lpc))
+
     def p1_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
         """Inflated frame bodies -> PCM: Golomb decode (profile1.py:59-64) and K8 on the device, one H2D copy of the
         bodies (about a byte per coefficient instead of the four of an int32 array)."""

@@ -574,3 +574,47 @@ def inflate_batch(src: torch.Tensor, offsets: torch.Tensor, dst_stride: int):
             _lib.load().inflate_raw(base, offsets.data_ptr(), n_frames, dst.data_ptr(), dst_stride, nbytes.data_ptr(),
                                     status.data_ptr(), _stream_ptr())
     return dst[:n_frames * dst_stride].view(n_frames, dst_stride), nbytes[:n_frames], status[:n_frames]
+
+
+# ---------------------------------------------------------------------------------------------
+# raw DEFLATE deflate (frad_deflate_raw): the zlib.compress(frad, wbits=-15) of profile1.py:50 / profile2.py:54
+# ---------------------------------------------------------------------------------------------
+DEFLATE_OK, DEFLATE_HOST, DEFLATE_OVERFLOW = 0, 1, 2
+DEFLATE_LIMIT = 65274            # wsize + MAX_DIST: bodies from this length on get DEFLATE_HOST
+
+
+def deflate_batch(src: torch.Tensor, offsets: torch.Tensor):
+    """zlib's raw deflate (level 6, memLevel 8, 15 window bits, default strategy) of a batch of bodies on the device.
+
+    ``src`` uint8 [total], ``offsets`` int64 [n_frames + 1] (both CUDA tensors): body i is ``src[offsets[i]:offsets[i+1]]``.
+    Returns ``(dst uint8 [n_frames, stride], dst_bytes int64 [n_frames], status int32 [n_frames])``: with status 0 row i's
+    first ``dst_bytes[i]`` bytes equal ``zlib.compressobj(-1, zlib.DEFLATED, -15)``'s ``compress(body) + flush()``; status 1
+    (``DEFLATE_HOST``) = the body is ``DEFLATE_LIMIT`` bytes or longer and is left to the host (nothing written to its row).
+    The stride is chosen from the longest body, with 4 bytes to spare for ``frad_rows_compact``'s word reads.  The offsets
+    are checked against ``src`` here (one device-to-host read), so no caller buffer reaches the kernel unchecked."""
+    _require_cuda(src, "src"); _require_cuda(offsets, "offsets")
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError(f"src must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries")
+    if offsets.device != src.device:
+        raise ValueError("src and offsets must be on the same device")
+    n_frames = offsets.numel() - 1
+    if n_frames > 0x7fffffff:
+        raise ValueError("at most 2^31 - 1 bodies per batch")
+    lens = offsets[1:] - offsets[:-1]
+    longest = lens.max() if n_frames else torch.zeros((), dtype=torch.int64, device=src.device)
+    lo, hi, mono, longest = torch.stack([offsets.min(), offsets.max(), (lens < 0).any().to(torch.int64), longest]).tolist()
+    if lo < 0 or hi > src.numel() or mono:
+        raise ValueError(f"offsets must be non-decreasing and within [0, {src.numel()}] (got min {lo}, max {hi})")
+    lib = _lib.load()
+    stride = lib.deflate_stride(min(longest, DEFLATE_LIMIT - 1) + 4)
+    dst = torch.empty(max(n_frames * stride, 16), dtype=torch.uint8, device=src.device)
+    nbytes = torch.empty(max(n_frames, 1), dtype=torch.int64, device=src.device)
+    status = torch.empty(max(n_frames, 1), dtype=torch.int32, device=src.device)
+    if n_frames:
+        base = src.data_ptr() if src.numel() else dst.data_ptr()   # (every body empty: nothing is read)
+        with torch.cuda.device(src.device):
+            lib.deflate_raw(base, offsets.data_ptr(), n_frames, dst.data_ptr(), stride, nbytes.data_ptr(), status.data_ptr(),
+                            _stream_ptr())
+    return dst[:n_frames * stride].view(n_frames, stride), nbytes[:n_frames], status[:n_frames]

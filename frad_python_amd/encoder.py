@@ -52,11 +52,14 @@ class EncodeResult:
 
 class Encoder:
     def __init__(self, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *, bridge=None,
-                 allow_profile2: bool = False, allow_ecc: bool = False):
+                 allow_profile2: bool = False, allow_ecc: bool = False, device_deflate: bool = False):
         # profile 2 (TNS) is outside the reference's AVAILABLE list; `allow_profile2=True` admits it on this instance only
         self.allow_profile2 = bool(allow_profile2)
         # `allow_ecc=True` makes set_ecc the reference's: Reed-Solomon protection of every frame, on the device
         self.allow_ecc = bool(allow_ecc)
+        # `device_deflate=True` (extension, opt-in): profiles 1 and 2 deflate on the device (frad_deflate_raw), byte-identical
+        # to zlib; profiles 0 and 4 ignore it
+        self.device_deflate = bool(device_deflate)
         if profile not in AVAILABLE and not (profile == 2 and self.allow_profile2):
             print(f"Invalid profile! Available: {AVAILABLE}", file=sys.stderr)
             sys.exit(1)
@@ -120,16 +123,22 @@ class Encoder:
             bits = self.bit_depth if self.bit_depth in _P2_DEPTHS else 16                    # profile2.py:16
             N = compact.get_samples_min_ge(n_eff)
             # DCT, masking, TNS analysis, quantiser and the three Golomb streams on the device; the host deflates and frames
-            bodies = self.bridge.p2_encode_bodies(pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate),
-                                                  self.loss_level, hop, n_valid)
-            out += self._emit_all([(frad, _P2_DEPTHS.index(bits), n_valid) for frad in _map_zlib(self._deflate, bodies)])
+            args = (pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate), self.loss_level, hop, n_valid)
+            if self.device_deflate:
+                payloads = self.bridge.p2_encode_payloads(*args)            # ... and the deflate as well
+            else:
+                payloads = _map_zlib(self._deflate, self.bridge.p2_encode_bodies(*args))
+            out += self._emit_all([(frad, _P2_DEPTHS.index(bits), n_valid) for frad in payloads])
         elif prof == 1:
             bits = self.bit_depth if self.bit_depth in _P1_DEPTHS else 16
             N = compact.get_samples_min_ge(n_eff)
             # quantiser and Exp-Golomb-Rice coder behind the bridge (on the device); the host only deflates (profile1.py:50) and frames
-            bodies = self.bridge.p1_encode_bodies(pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate),
-                                                  self.loss_level, hop, n_valid)
-            out += self._emit_all([(frad, _P1_DEPTHS.index(bits), n_valid) for frad in _map_zlib(self._deflate, bodies)])
+            args = (pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate), self.loss_level, hop, n_valid)
+            if self.device_deflate:
+                payloads = self.bridge.p1_encode_payloads(*args)            # ... and the deflate as well
+            else:
+                payloads = _map_zlib(self._deflate, self.bridge.p1_encode_bodies(*args))
+            out += self._emit_all([(frad, _P1_DEPTHS.index(bits), n_valid) for frad in payloads])
         else:
             bits = self.bit_depth if self.bit_depth in _LOSSLESS_DEPTHS else 16
             whole = getattr(self.bridge, "lossless_encode_stream", None)

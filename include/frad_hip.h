@@ -253,6 +253,29 @@ int frad_p2_golomb_encode(const int32_t* q, const int32_t* tq, const int32_t* lp
 int frad_inflate_raw(const void* src, const int64_t* src_offsets, int64_t n_frames, void* dst, int64_t dst_stride,
                      int64_t* dst_bytes, int32_t* status, void* stream);
 
+/* ---- raw DEFLATE deflate (row 8f #1): zlib.compress(frad, wbits=-15) of the compact profiles (profile1.py:50,
+ * profile2.py:54), i.e. zlib.compressobj(-1, zlib.DEFLATED, -15): compress(body) + flush() ------------------------------------
+ * frad_deflate_raw: frame i's body src[src_offsets[i] .. src_offsets[i+1]) is deflated into dst + i*dst_stride.
+ *   status[i]     0 = ok: the row's first dst_bytes[i] bytes are exactly zlib's raw deflate of the body at level 6
+ *                     (Z_DEFAULT_COMPRESSION: lazy matching, good 8 / lazy 16 / nice 128 / chain 128), memLevel 8, window
+ *                     bits 15, Z_DEFAULT_STRATEGY;
+ *                 1 = the body is 65 274 bytes or longer (wsize + MAX_DIST, where zlib starts sliding its window): it is
+ *                     not deflated here, the caller deflates it on the host;
+ *                 2 = the body is longer than dst_stride admits (frad_deflate_stride of its length exceeds dst_stride).
+ *                 With a non-zero status dst_bytes[i] = 0 and nothing is written to the row.
+ * dst_stride: a multiple of 16, at least frad_deflate_stride(longest body) = round16(n + 6 * (n / 16383 + 1) + 1): zlib's
+ * worst case for n bytes, stored blocks included (each of the at most n / 16383 + 1 blocks adds at most 42 bits, the
+ * final byte boundary at most 7).  dst 16-byte aligned; dst_bytes int64 [n_frames], status int32 [n_frames].  Only the
+ * bytes [0, dst_bytes[i]) of a row are written; the source is read bytewise and never outside
+ * [src_offsets[0], src_offsets[n_frames]), so neither buffer needs slack.  FRAD_E_INVALID for a NULL pointer or a stride /
+ * alignment outside these rules.  One wave per frame; LDS per wave about 12.5 KiB + 6 B per byte of the longest body the
+ * stride admits (the body itself is read from global memory when that would exceed 160 KiB).
+ * frad_deflate_stride: the smallest dst_stride for bodies of at most max_body_bytes bytes (lengths of 65 274 and more
+ * count as 65 273: such bodies get status 1); FRAD_E_INVALID for a negative length. */
+int frad_deflate_raw(const void* src, const int64_t* src_offsets, int64_t n_frames, void* dst, int64_t dst_stride,
+                     int64_t* dst_bytes, int32_t* status, void* stream);
+int64_t frad_deflate_stride(int64_t max_body_bytes);
+
 /* ---- frame header checksum (row 8f #1) --------------------------------------------------------
  * crc_out[i] = zlib.crc32 of the `nbytes` payload bytes of frame i (at data + i*stride), the value
  * ASFH.write puts into a lossless frame's header (src/libfrad/tools/asfh.py:51-73), so a batch's
