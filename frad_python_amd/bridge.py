@@ -314,6 +314,54 @@ class HipBridge:
             pcm = out.cpu().numpy().reshape(-1, C)
         return pcm, nxt.cpu().numpy()
 
+    # ------------------------------------------------------------------ group-level helpers of decode_batch (batch.py)
+    # The frames of every stream of a group go through each stage in one call; what comes back stays on the device until
+    # clips_overlap_add has assembled the ragged output.
+    def compact_frames_dev(self, profile, bodies: list, N, C, bits, srate):
+        """inflated bodies of any number of streams -> float64 frames [n, N, C] on the device: one upload, one Golomb decode,
+        one K8 / p2 synthesis + inverse DCT (an empty body is a frame of zeros, profile1.py:59-60)"""
+        t = self.torch
+        off = np.zeros(len(bodies) + 1, np.int64)
+        np.cumsum([len(b) for b in bodies], out=off[1:])
+        flat = self._up(b"".join(bodies) + bytes(8))              # aligned 32-bit word reads: tail slack (frad_hip.h)
+        return self._frames_dev(profile, flat, t.from_numpy(off).to(self.device), N, C, bits, srate)
+
+    def deflated_frames_dev(self, profile, payloads: list, N, C, bits, srate):
+        """``compact_frames_dev`` from the deflated payloads, inflated on the device; None when a frame does not inflate"""
+        got = self.inflate_run(payloads, profile, N, C)
+        if got is None:
+            return None
+        return self._frames_dev(profile, *got, N, C, bits, srate)
+
+    def lossless_frames_dev(self, profile, payloads: list, N, C, bits, little_endian):
+        """equally long profile-0 / 4 payloads -> float64 frames [n, N, C] on the device: one upload, one launch"""
+        n, nb = len(payloads), len(payloads[0])
+        stride = (nb + 15) // 16 * 16
+        host = np.zeros((n, stride), np.uint8)
+        host[:, :nb] = np.frombuffer(b"".join(payloads), np.uint8).reshape(n, nb)
+        dev = self.torch.from_numpy(host).to(self.device)
+        return self.core.digital_batch(profile, dev, n, N, C, bits, little_endian)
+
+    def clips_overlap_add(self, frames, clip_frame0, N, C, ratio, tails: list, tail_off, tail_rows, out_format=None, tail_win=None,
+                          as_tensor=False):
+        """The clips' cross-fade, concatenation and output conversion in one launch (core.clips_overlap_add).  ``frames``: a
+        device tensor from the helpers above (or an ndarray), ``tails``: the last-frame tensors, concatenated here in the order
+        ``tail_off`` counts them.  -> (out, out_off): a device tensor with ``as_tensor``, else one download into an ndarray
+        [rows, C] of float64 or of ``out_format``'s dtype."""
+        from .backend.pcmformat import ff_format_to_numpy_type
+        t = self.torch
+        dev = lambda a: a if isinstance(a, t.Tensor) else t.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
+        frames = dev(frames) if frames is not None else None
+        tails = [dev(x).reshape(-1) for x in tails]
+        flat = None if not tails else tails[0] if len(tails) == 1 else t.cat(tails)
+        out, out_off = self.core.clips_overlap_add(frames, clip_frame0, N, C, ratio, flat, tail_off, tail_rows, out_format, tail_win)
+        if as_tensor:
+            return out, out_off
+        if out_format is None:
+            return self._down_array(out, np.float64, (-1, C)) if out.numel() else np.zeros((0, C)), out_off
+        dt = ff_format_to_numpy_type(out_format)
+        return self._down_array(out, dt, (-1, C)) if out.numel() else np.zeros((0, C), dt), out_off
+
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch
         return self.core.p1_digital_batch(t.from_numpy(np.ascontiguousarray(q, np.int32)).to(self.device),

@@ -534,6 +534,89 @@ def p1_overlap_add(frames: torch.Tensor, overlap_ratio: int, prev_tail: torch.Te
     return out, nxt
 
 
+def clips_overlap_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, overlap_ratio: int, tails: torch.Tensor | None = None,
+                      tail_off=None, tail_rows=None, out_format: str | None = None, tail_win=None) -> torch.Tensor:
+    """``Decoder.overlap`` + ``flush()`` (decoder.py:28-46, 110-114) for many independent clips in one launch, with ragged
+    output (frad_clips_overlap_add).
+
+    ``frames`` float64 [n_frames, N, C]: the equal-length decoded frames, clip after clip; ``clip_frame0`` (host integers,
+    n_clips + 1, non-decreasing from 0 to n_frames) says which belong to clip j.  ``tails`` flat float64: clip j's last frame of
+    another length is ``tail_rows[j]`` rows of C at element offset ``tail_off[j]`` (0 rows: none).  ``overlap_ratio`` 0: no
+    fade (cut = N); 2..256: the Hann cross-fade of ``p1_overlap_add`` inside each clip, first frames unfaded, the flush fragment
+    appended.  ``tail_win``: see include/frad_hip.h.  Returns ``(out, out_off)``: ``out`` float64 [rows, C], or with
+    ``out_format`` a uint8 tensor of that format's bytes as ``p1_overlap_add`` returns them; clip j is rows
+    ``out_off[j]:out_off[j+1]`` (numpy int64).  The index arrays are checked here, on the host, before anything is launched."""
+    cf = np.ascontiguousarray(clip_frame0, np.int64).reshape(-1)
+    n_clips = cf.size - 1
+    if n_clips < 0:
+        raise ValueError("clip_frame0 needs n_clips + 1 entries")
+    if N < 1 or C < 1 or not (overlap_ratio == 0 or 2 <= overlap_ratio <= 256):
+        raise ValueError(f"bad geometry: N={N} C={C} overlap_ratio={overlap_ratio}")
+    n_frames = int(cf[-1])
+    if cf[0] != 0 or (np.diff(cf) < 0).any():
+        raise ValueError("clip_frame0 must start at 0 and not decrease")
+    if n_frames:
+        if frames is None:
+            raise ValueError("frames is missing")
+        _require_cuda(frames, "frames")
+        if frames.dtype != torch.float64 or frames.numel() != n_frames * N * C:
+            raise ValueError(f"frames must be float64 [{n_frames}, {N}, {C}]")
+    device = frames.device if frames is not None else (tails.device if tails is not None else torch.device("cuda", torch.cuda.current_device()))
+    tr = np.zeros(n_clips, np.int32) if tail_rows is None else np.ascontiguousarray(tail_rows, np.int32).reshape(-1)
+    to = np.zeros(n_clips, np.int64) if tail_off is None else np.ascontiguousarray(tail_off, np.int64).reshape(-1)
+    if tr.size != n_clips or to.size != n_clips:
+        raise ValueError("tail_off and tail_rows need one entry per clip")
+    cut = N * (overlap_ratio - 1) // overlap_ratio if overlap_ratio else N
+    L = N - cut
+    if ((tr < 0) | ((tr > 0) & (tr < L))).any():
+        raise ValueError(f"a last frame needs at least L = {L} rows")
+    has = tr > 0
+    if has.any():
+        if tails is None:
+            raise ValueError("tails is missing")
+        _require_cuda(tails, "tails")
+        if tails.dtype != torch.float64:
+            raise TypeError("tails must be float64")
+        if (to[has] < 0).any() or (to[has] + tr[has].astype(np.int64) * C > tails.numel()).any():
+            raise ValueError("a last frame lies outside tails")
+    m = np.diff(cf)
+    rows = m * cut + np.where(has, tr.astype(np.int64), np.where(m > 0, L, 0))
+    out_off = np.zeros(n_clips + 1, np.int64)
+    np.cumsum(rows, out=out_off[1:])
+    total = int(out_off[-1])
+    win = None
+    if tail_win is not None and L:
+        win = np.ascontiguousarray(tail_win, np.float64).reshape(-1)
+        if win.size != L:
+            raise ValueError(f"tail_win must hold L = {L} weights")
+    code = pcm_dtype_code(out_format) if out_format is not None else pcm_dtype_code("f64le")
+    if out_format is None:
+        out = torch.empty((total, C), dtype=torch.float64, device=device)
+    else:
+        nb = total * C * itemsize_of(code)
+        out = torch.empty(nb + 16, dtype=torch.uint8, device=device)[:nb]
+    if total == 0 or n_clips == 0:
+        return out, out_off
+    # the four index tables (and the window) in one upload: int64 clip_frame0 | out_off | tail_off | float64 window | int32 tail_rows
+    n1 = n_clips + 1
+    nw = win.size if win is not None else 0
+    table = np.empty(8 * (2 * n1 + n_clips + nw) + 4 * n_clips, np.uint8)
+    table[:8 * n1] = cf.view(np.uint8)
+    table[8 * n1:16 * n1] = out_off.view(np.uint8)
+    table[16 * n1:16 * n1 + 8 * n_clips] = to.view(np.uint8)
+    w0 = 16 * n1 + 8 * n_clips
+    if nw:
+        table[w0:w0 + 8 * nw] = win.view(np.uint8)
+    table[w0 + 8 * nw:] = tr.view(np.uint8)
+    dev = torch.from_numpy(table).to(device)
+    p = dev.data_ptr()
+    with torch.cuda.device(device):
+        _lib.load().clips_overlap_add(frames.data_ptr() if n_frames else 0, p, n_clips, N, C, overlap_ratio,
+                                      tails.data_ptr() if tails is not None else 0, p + 16 * n1, p + w0 + 8 * nw, p + w0 if nw else 0,
+                                      code, out.data_ptr(), p + 8 * n1, total, _stream_ptr())
+    return out, out_off
+
+
 # ---------------------------------------------------------------------------------------------
 # raw DEFLATE inflate (frad_inflate_raw): the zlib.decompress(frad, wbits=-15) of profile1.py:59 / profile2.py:61-64
 # ---------------------------------------------------------------------------------------------

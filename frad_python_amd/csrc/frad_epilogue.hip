@@ -109,6 +109,140 @@ __global__ void __launch_bounds__(256) k_p1_ola_pcm(const double* __restrict__ f
             next_tail[i] = frames[((n_frames - 1) * N + cut) * C + i];
 }
 
+// One output row of the clip-aware overlap-add: where row r of a clip (of m * cut + tail rows, or + L flush rows) comes from.
+// Decoder.overlap + flush() (decoder.py:28-46, 110-114) per clip: the equal-length frames cross-fade as p1_ola_value does (same
+// operation order, same cos arguments), the clip's first frame is not faded, a last frame of another length is faded over its
+// first L rows and written whole, and without one the last frame's rows [cut, N) follow unfaded.  `tail_win` (optional,
+// hanning_in_overlap(L) as the host computes it): the weights of a last frame whose own overlap length differs from L -- the
+// frame the Decoder cross-fades on the host, in numpy, because the carried fragment has another geometry (decoder.py:207-209).
+struct ClipRow {
+    const double* src;                                         // the row's C samples
+    const double* prev;                                        // the row it is faded against, or nullptr
+    double w_in, w_out;
+};
+struct ClipCur {                                               // the clip a lane is in: its tables' entries, read once per clip
+    long long j, base, end, f0, m, toff;
+    int rows;
+};
+
+__device__ __forceinline__ ClipRow clips_ola_row(const double* __restrict__ frames, int N, int C, int cut, int ratio,
+                                                 const double* __restrict__ tails, const double* __restrict__ tail_win, const ClipCur& k,
+                                                 long long r) {
+    const int L = N - cut;
+    const double pi = 3.141592653589793;
+    const long long body = k.m * cut;
+    ClipRow o;
+    o.prev = nullptr; o.w_in = 1.0; o.w_out = 0.0;
+    bool table = false;
+    int n;
+    if (r < body) {
+        long long f;
+        if (r <= 0x7fffffffLL) { f = (uint32_t)r / (uint32_t)cut; n = (int)((uint32_t)r - (uint32_t)f * (uint32_t)cut); }
+        else { f = r / cut; n = (int)(r - f * cut); }
+        o.src = frames + ((k.f0 + f) * N + n) * C;
+        if (n < L && f > 0) o.prev = frames + ((k.f0 + f - 1) * N + cut + n) * C;
+    } else {
+        const long long t = r - body;
+        n = t < L ? (int)t : L;
+        if (k.rows > 0) {
+            o.src = tails + k.toff + t * C;
+            if (t < L && k.m > 0) {
+                o.prev = frames + ((k.f0 + k.m - 1) * N + cut + n) * C;
+                table = tail_win != nullptr && k.rows - (int)((long long)k.rows * (ratio - 1) / ratio) != L;
+            }
+        } else {
+            o.src = frames + ((k.f0 + k.m - 1) * N + cut + t) * C;       // the flush fragment
+        }
+    }
+    if (o.prev != nullptr) {
+        if (table) { o.w_in = tail_win[n]; o.w_out = tail_win[L - 1 - n]; }
+        else {
+            o.w_in = 0.5 * (1.0 - cos(pi * (double)(n + 1) / (double)(L + 1)));
+            o.w_out = 0.5 * (1.0 - cos(pi * (double)(L - n) / (double)(L + 1)));
+        }
+    }
+    return o;
+}
+
+// frad_clips_overlap_add: a streaming pass over the ragged output.  A block owns a tile of CLIPS_K * 256 stores of 16 bytes, a
+// lane every 256th of them.  The lane finds the clip of its first sample-frame by a binary search over out_off (the table
+// stays in L2), keeps the clip's table entries in registers and searches again only when a store has left the clip, so no
+// element searches from the start; where a row comes from and its two Hann weights are worked out once per row, not per
+// sample.  Every decoded row is read once (a frame's last L rows only by the fade of the next frame, or as the flush fragment)
+// and every output sample written once, 16 bytes per lane where the output allows it.
+constexpr int CLIPS_K = 4;
+template <int KIND, int LGS>
+__global__ void __launch_bounds__(256) k_clips_ola(const double* __restrict__ frames, const int64_t* __restrict__ clip_frame0, long long n_clips,
+                                                   int N, int C, int cut, int ratio, const double* __restrict__ tails,
+                                                   const int64_t* __restrict__ tail_off, const int32_t* __restrict__ tail_rows,
+                                                   const double* __restrict__ tail_win, unsigned char* __restrict__ out,
+                                                   const int64_t* __restrict__ out_off, long long out_rows, int be, int raw_be) {
+    constexpr int EPT = 16 >> LGS;
+    long long last = out_off[n_clips];
+    if (last > out_rows) last = out_rows;                      // never beyond what the caller sized
+    const long long n = last * C, n0 = (long long)out_off[0] * C;
+    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long tile = 256LL * EPT * CLIPS_K;
+    auto enter = [&](ClipCur& k, long long j) {
+        k.j = j; k.base = out_off[j]; k.end = out_off[j + 1];
+        k.f0 = clip_frame0[j]; k.m = clip_frame0[j + 1] - k.f0; k.rows = tail_rows[j]; k.toff = tail_off[j];
+    };
+    for (long long t0 = (long long)blockIdx.x * tile; t0 < n; t0 += (long long)gridDim.x * tile) {
+        ClipCur k;
+        k.j = -1; k.end = 0;
+        for (int it = 0; it < CLIPS_K; ++it) {
+            const long long i0 = t0 + ((long long)it * 256 + threadIdx.x) * EPT;
+            if (i0 >= n) break;
+            long long s;
+            if (n <= 0x7fffffffLL) s = (uint32_t)i0 / (uint32_t)C; else s = i0 / C;
+            int c = (int)(i0 - s * C);
+            if (k.j < 0 || s >= k.end) {                       // the last clip that starts at or before sample-frame s
+                long long lo = k.j < 0 ? 0 : k.j, hi = n_clips;
+                while (hi - lo > 1) {
+                    const long long mid = (lo + hi) >> 1;
+                    if ((long long)out_off[mid] <= s) lo = mid; else hi = mid;
+                }
+                enter(k, lo);
+            }
+            ClipRow row;
+            row.src = nullptr; row.prev = nullptr; row.w_in = 1.0; row.w_out = 0.0;
+            u64 b[EPT];
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) {
+                double x = 0.0;
+                if (i0 + e < n && i0 + e >= n0) {
+                    if (row.src == nullptr || c == 0) {
+                        while (s >= k.end && k.j + 1 < n_clips) enter(k, k.j + 1);
+                        row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, k, s - k.base);
+                    }
+                    x = row.src[c];
+                    if (row.prev != nullptr) {
+                        x = x * row.w_in;
+                        x = x + row.prev[c] * row.w_out;
+                    }
+                }
+                b[e] = from_f64_bits<KIND, LGS>(x, raw_be != 0 && be);
+                if (be) b[e] = swap_elem<LGS>(b[e]);
+                if (++c == C) { c = 0; ++s; }
+            }
+            if (vec && i0 + EPT <= n && i0 >= n0) {
+                v4u q = {0, 0, 0, 0};
+#pragma unroll
+                for (int e = 0; e < EPT; ++e) {
+                    if constexpr (LGS == 3) { q[2 * e] = (uint32_t)b[e]; q[2 * e + 1] = (uint32_t)(b[e] >> 32); }
+                    else if constexpr (LGS == 2) q[e] = (uint32_t)b[e];
+                    else if constexpr (LGS == 1) q[e >> 1] |= (uint32_t)b[e] << (16 * (e & 1));
+                    else q[e >> 2] |= (uint32_t)b[e] << (8 * (e & 3));
+                }
+                FRAD_NT_STORE(q, FRAD_GPTR(v4u, out + (i0 << LGS)));
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPT; ++e) if (i0 + e < n && i0 + e >= n0) store_elem<LGS>(out + ((i0 + e) << LGS), b[e]);
+            }
+        }
+    }
+}
+
 template <int SRC>
 int launch_from_f64(int dtype, const unsigned char* in, unsigned char* out, long long n, const Geom& g, hipStream_t s) {
     const int kind = dtype >> 3, lg = (dtype >> 1) & 3, be = dtype & 1;
@@ -268,6 +402,36 @@ int frad_p1_overlap_add_pcm(const double* frames, int64_t n_frames, int32_t N, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned char* o = static_cast<unsigned char*>(ola_out);
 #define GO(K, L) hipLaunchKernelGGL((k_p1_ola_pcm<K, L>), grid, blk, 0, s, frames, (long long)n_frames, N, C, cut, prev_tail, o, next_tail, be, raw)
+    switch (kind * 4 + lg) {
+        case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
+        case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;
+        case 9: GO(2, 1); break; case 10: GO(2, 2); break; case 11: GO(2, 3); break;
+        default: return FRAD_E_INVALID;
+    }
+#undef GO
+    EPICHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
+                           const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
+                           int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off, int64_t out_rows, void* stream) {
+    if (!valid_out_dtype(out_dtype) || n_clips < 0 || out_rows < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
+    if (overlap_ratio != 0 && (overlap_ratio < 2 || overlap_ratio > 256)) return FRAD_E_INVALID;
+    if (n_clips == 0 || out_rows == 0) return FRAD_OK;
+    if (!clip_frame0 || !tail_off || !tail_rows || !out_off || !out) return FRAD_E_INVALID;
+    const int cut = overlap_ratio ? (int)((long long)N * (overlap_ratio - 1) / overlap_ratio) : N;     // decoder.py:44
+    const int ratio = overlap_ratio ? overlap_ratio : 1;
+    const int kind = out_dtype >> 3, lg = (out_dtype >> 1) & 3, be = out_dtype & 1, raw = (flags & FRAD_RAW_BE_INTS) ? 1 : 0;
+    const long long total = (long long)out_rows * C, per_block = 256LL * (16 >> lg) * CLIPS_K;
+    long long blocks = (total + per_block - 1) / per_block;
+    if (blocks > 16384) blocks = 16384;
+    if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks), blk(256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned char* o = static_cast<unsigned char*>(out);
+#define GO(K, L) hipLaunchKernelGGL((k_clips_ola<K, L>), grid, blk, 0, s, frames, clip_frame0, (long long)n_clips, N, C, cut, ratio, tails, \
+                                    tail_off, tail_rows, tail_win, o, out_off, (long long)out_rows, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
         case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;

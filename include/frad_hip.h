@@ -337,6 +337,30 @@ int frad_p1_overlap_add_pcm(const double* frames, int64_t n_frames, int32_t N, i
                             int32_t out_dtype, uint32_t flags, void* ola_out, double* next_tail, void* stream);
 int frad_p1_digital_pcm(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
                         int32_t srate, int32_t out_dtype, uint32_t flags, void* pcm_out, void* stream);
+/* frad_clips_overlap_add == Decoder.overlap + flush() (decoder.py:28-46, 110-114) for n_clips independent streams in one pass,
+ * with ragged output and the output conversion of frad_p1_overlap_add_pcm (all arrays in device memory).
+ *   frames      float64 [clip_frame0[n_clips], N, C]: the equal-length frames, clip after clip; clip j owns frames
+ *               [clip_frame0[j], clip_frame0[j+1]) (m_j of them, m_j >= 0)
+ *   tails       float64: clip j's last frame of another length is tail_rows[j] rows of C at ELEMENT offset tail_off[j];
+ *               tail_rows[j] == 0: the clip has none
+ *   out         out_dtype (FRAD_PCM_*, flags as frad_p1_overlap_add_pcm): clip j's samples start at sample-frame out_off[j], and
+ *               out_off[j+1] - out_off[j] == m_j * cut + (tail_rows[j] ? tail_rows[j] : (m_j ? N - cut : 0)); out_off has
+ *               n_clips + 1 entries, out_rows == out_off[n_clips] (the host's copy: it sizes the launch, and nothing beyond
+ *               min(out_rows, out_off[n_clips]) sample-frames is written); sample-frames before out_off[0] are left alone
+ *   overlap_ratio 0: cut = N, no fade (lossless profiles and ratio 0: a ragged gather + conversion)
+ *   overlap_ratio 2..256: cut = N*(ratio-1)/ratio, L = N - cut.  Inside a clip, frame i > 0 is cross-faded over its first L
+ *               rows against rows [cut, N) of frame i-1 with hanning_in_overlap(L) (backend/__init__.py:3), the values of
+ *               frad_p1_overlap_add; a clip's first frame is not faded; the last frame of another length is faded over its first
+ *               L rows against the last equal-length frame (not when m_j == 0) and written whole; without one, rows [cut, N) of
+ *               the last frame follow unfaded (the flush fragment).  Requires tail_rows[j] == 0 or >= L.
+ *   tail_win    optional float64 [L]: hanning_in_overlap(L) as the caller computed it.  When given, it weights the last frames
+ *               whose own overlap length tail_rows - tail_rows*(ratio-1)/ratio differs from L: the Decoder cross-fades those
+ *               on the host, because the carried fragment has another geometry (decoder.py:207-209), and this keeps the result
+ *               bit-identical to it.  NULL: every weight is computed on the device.
+ * The offsets are the caller's to check (core.clips_overlap_add does); FRAD_E_INVALID for N, C, the ratio and the dtype.      */
+int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
+                           const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
+                           int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off, int64_t out_rows, void* stream);
 
 /* frad_asfh_scan: HOST code (no device involved).  One pass over a FrAD byte stream from `start`: resynchronises on
  * FRM_SIGN and parses every header as ASFH.read does (tools/asfh.py:98-134; the search as decoder.py:82-90), filling
