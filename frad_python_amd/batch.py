@@ -9,14 +9,12 @@ reference's caller drives it (src/decoder.py:70-88); a stream that does not have
 writes is decoded by such a ``Decoder`` and listed in ``res.fallback``."""
 from __future__ import annotations
 
-import zlib
-
 import numpy as np
 
-from . import ecc
 from .backend.pcmformat import ff_format_to_numpy_type, from_f64
-from .decoder import (_BUILT, _DEFLATED, _LOSSLESS_DEPTHS, _P1_DEPTHS, _P2_DEPTHS, Decoder, _Damaged, _lossless_frame_len,
-                      _strip_ecc)
+from .decoder import Decoder
+from .fourier import BIT_DEPTHS
+from .frames import BUILT, DEFLATED, classify, inflate_bodies, repair
 
 _SCAN_END, _SCAN_TABLE_FULL = 0, 3                          # include/frad_hip.h
 
@@ -93,41 +91,28 @@ def _scan_together(scan, streams: list):
     return joined, [None if bad[j] else rows_of[j] for j in range(n)]
 
 
-def _payload_bytes(values: int, bits: int) -> int:
-    return (values * bits + 7) // 8
-
-
 def _plan(rows: list, joined: bytes, fix_error: bool):
     """The batched shape (module docstring), checked on the scanner's rows of one stream; None: the per-stream Decoder."""
     frames, flushed = [], False
-    for (h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc) in rows:
+    for row in rows:
+        h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc = row
         if fflush:
             flushed = True
             continue
-        if flushed or profile not in _BUILT or ch < 1 or fsize < 1:
+        if flushed or profile not in BUILT or ch < 1 or fsize < 1 or depth >= len(BIT_DEPTHS[profile]):
             return None
-        depths = _P1_DEPTHS if profile == 1 else _P2_DEPTHS if profile == 2 else _LOSSLESS_DEPTHS
-        if depth >= len(depths):
+        if is_ecc and not 1 <= dsize + csize <= 255:
             return None
-        frad, nb = joined[p_off:p_off + p_len], p_len
-        if is_ecc:
-            if not 1 <= dsize + csize <= 255:
-                return None
-            if fix_error and ecc.needs_repair(profile, frad, crc):
-                frad, nb = _Damaged(frad, dsize, csize), ecc.data_len(len(frad), dsize, csize)
-            else:
-                frad = _strip_ecc(frad, dsize, csize)
-                nb = len(frad)
-        if profile in _DEFLATED:
+        key, (frad, _, nb) = classify(joined, row, fix_error)
+        if profile in DEFLATED:
             if ratio == 1:
                 return None
-            key = (profile, fsize, ch, depth, bool(le), srate, ratio, None)
+            key += (None,)
         else:
-            n_eff = _lossless_frame_len(nb, depth, ch, fsize)
-            if nb == 0 or _payload_bytes(n_eff * ch, depths[depth]) != nb:
-                return None
-            key = (profile, n_eff, ch, depth, bool(le), srate, 0, nb)       # equal payload length: Decoder._process
-        frames.append((key, frad))
+            if nb == 0 or (key[1] * ch * BIT_DEPTHS[profile][depth] + 7) // 8 != nb:
+                return None                                   # no whole payload
+            key += (nb,)                                      # equal payload length: the Decoder's run-break rule
+        frames.append((key, frad if frad is not None else joined[p_off:p_off + p_len]))
     p = _Plan()
     p.frames, p.key, p.main, p.tail_key, p.tail = len(frames), None, [], None, None
     p.srate, p.channels = (rows[-1][8], rows[-1][7]) if rows else (0, 0)
@@ -171,30 +156,20 @@ def _frames(bridge, key, payloads: list, device_inflate: bool):
     """The frames of a whole group through the decode stages in one call each -> float64 [n, N, C], a device tensor when the
     bridge keeps them there (HipBridge), else an ndarray (a bridge built from the per-run methods)."""
     profile, N, C, depth, endian, srate = key[:6]
-    if profile not in _DEFLATED:
-        on_dev = getattr(bridge, "lossless_frames_dev", None)
-        fn = on_dev if on_dev is not None else bridge.lossless_decode
-        return fn(profile, payloads, N, C, _LOSSLESS_DEPTHS[depth], endian)
-    bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth]
-    if device_inflate:
-        fn = getattr(bridge, "deflated_frames_dev", None)
-        got = fn(profile, payloads, N, C, bits, srate) if fn is not None else None
+    bits = BIT_DEPTHS[profile][depth]
+    on_dev = getattr(bridge, "compact_decode", None)
+    if profile not in DEFLATED:
+        if on_dev is None:
+            return bridge.lossless_decode(profile, payloads, N, C, bits, endian)
+        return bridge.lossless_decode(profile, payloads, N, C, bits, endian, keep=True)
+    if device_inflate and on_dev is not None:
+        got = on_dev(profile, payloads, N, C, bits, srate, deflated=True, keep=True)
         if got is not None:
             return got                                        # else: a frame does not inflate there -> the host inflate, as a whole
-
-    def inflate(frad):
-        try:
-            return zlib.decompress(frad, wbits=-15)
-        except Exception:
-            return None                                       # profile1.py:59-60, profile2.py:63-64 -> a frame of zeros
-    from .encoder import _map_zlib
-    bodies = _map_zlib(inflate, payloads)
-    bad = [i for i, b in enumerate(bodies) if b is None]
-    bodies = [b if b is not None else b"" for b in bodies]
-    on_dev = getattr(bridge, "compact_frames_dev", None)
+    bodies, bad = inflate_bodies(payloads)
     if on_dev is not None:
-        return on_dev(profile, bodies, N, C, bits, srate)     # an empty body decodes to a frame of zeros
-    pcm = (bridge.p1_decode_bodies if profile == 1 else bridge.p2_decode_bodies)(bodies, N, C, bits, srate)
+        return on_dev(profile, bodies, N, C, bits, srate, keep=True)      # an empty body decodes to a frame of zeros
+    pcm = getattr(bridge, f"p{profile}_decode_bodies")(bodies, N, C, bits, srate)
     for i in bad:
         pcm[i] = 0.0
     return pcm
@@ -228,19 +203,6 @@ def clips_overlap_host(frames, clip_frame0, N, C, ratio, tails: list, tail_off, 
     return out, np.asarray(out_off, np.int64)
 
 
-def _repair(bridge, payloads: list) -> list:
-    """The damaged ECC payloads of a whole chunk: one ``rs_repair`` per stored ratio (Decoder._repair, across streams)."""
-    groups = {}
-    for i, p in enumerate(payloads):
-        if isinstance(p, _Damaged):
-            groups.setdefault((p.dsize, p.codesize), []).append(i)
-    for (dsize, csize), idx in groups.items():
-        fixed, _, _ = bridge.rs_repair([payloads[i].frad for i in idx], dsize, csize)
-        for i, f in zip(idx, fixed):
-            payloads[i] = f
-    return payloads
-
-
 def _decode_chunk(bridge, key, plans: list, out_format, device_inflate, as_tensor):
     """-> (out, out_off): the chunk's ragged PCM, stream j of ``plans`` at rows out_off[j]:out_off[j+1]"""
     profile, N, C = key[:3]
@@ -252,7 +214,7 @@ def _decode_chunk(bridge, key, plans: list, out_format, device_inflate, as_tenso
         if p.tail_key is not None:
             tails_by.setdefault(p.tail_key, []).append(j)
     order = [j for js in tails_by.values() for j in js]
-    fixed = _repair(bridge, main + [plans[j].tail for j in order])
+    fixed = repair(bridge, main + [plans[j].tail for j in order])
     main, tail_payloads = fixed[:len(main)], fixed[len(main):]
     frames = _frames(bridge, key, main, device_inflate) if main else None
     tails, tail_off, tail_rows = [], np.zeros(len(plans), np.int64), np.zeros(len(plans), np.int32)

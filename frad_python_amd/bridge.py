@@ -4,7 +4,19 @@
 them over) through the HIP transform core: one H2D copy, one launch per homogeneous batch, one D2H
 copy.  The Encoder / Decoder only depend on this small interface, which lets the CPU-only test-suite
 drive their host logic (frame cut, overlap carry, ASFH, CRC) with a bridge of its own; the default
--- and the only one in this package -- is the HIP one: there is no CPU fallback."""
+-- and the only one in this package -- is the HIP one: there is no CPU fallback.
+
+The seam is duck-typed (no base class); a bridge is whatever has the methods its user calls:
+  * Decoder / decode_batch: ``lossless_decode``, ``p1_decode_bodies`` / ``p2_decode_bodies`` (the profiles decoded) and
+    ``overlap_add``; ``rs_repair`` for fix_error=True.  Optional, probed with ``getattr``: ``scan_lib`` (the native header
+    scanner; without it the byte-wise parser runs and decode_batch goes stream by stream), ``lossless_decode_strided``,
+    ``p1_decode_run`` / ``p2_decode_run`` (the fused run), ``compact_decode`` (HipBridge only: device inflate, and frames
+    that stay on the device for decode_batch), ``clips_overlap_add``, ``torch`` + ``device`` (as_tensor).
+  * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
+    ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
+    and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
+  * Repairer: ``scan_lib``, ``rs_repair``, ``rs_encode``.
+``p1_encode`` and ``p1_decode`` move the bare integers (tests and tools)."""
 from __future__ import annotations
 
 import numpy as np
@@ -113,40 +125,50 @@ class HipBridge:
         out = self.core.digital_batch(profile, dev, n_frames, N, C, bits, little_endian, payload_stride=stride)
         return self._down_array(out, np.float64, (n_frames, N, C))
 
-    def lossless_decode(self, profile, payloads: list, N, C, bits, little_endian) -> np.ndarray:
-        n = len(payloads)
-        nb = len(payloads[0])
+    def lossless_decode(self, profile, payloads: list, N, C, bits, little_endian, keep=False):
+        """equally long profile-0 / 4 payloads -> float64 frames [n, N, C]: one upload, one launch, one download; with
+        ``keep`` they stay on the device (decode_batch)"""
+        n, nb = len(payloads), len(payloads[0])
         stride = (nb + 15) // 16 * 16
         host = np.zeros((n, stride), np.uint8)
-        for i, p in enumerate(payloads):
-            host[i, :nb] = np.frombuffer(p, np.uint8)
-        dev = self.torch.from_numpy(host).to(self.device)
-        return self.core.digital_batch(profile, dev, n, N, C, bits, little_endian).cpu().numpy()
+        host[:, :nb] = np.frombuffer(b"".join(payloads), np.uint8).reshape(n, nb)
+        frames = self.core.digital_batch(profile, self.torch.from_numpy(host).to(self.device), n, N, C, bits, little_endian)
+        return frames if keep else frames.cpu().numpy()
 
     def p1_encode(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True):
         q, tq = self.core.p1_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
                                             frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
         return q.cpu().numpy(), tq.cpu().numpy()
 
-    def p1_encode_bodies(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
-        """K7 + the Exp-Golomb-Rice stage on the device: the pre-deflate body of every frame (profile1.py:15-45),
-        one D2H copy of exactly those bytes; the integers never leave the device."""
-        q, tq = self.core.p1_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
-                                            frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
-        flat, offsets = self.core.p1_golomb_encode_batch(q, tq)
-        off = offsets.cpu().numpy()
-        host = self._down_bytes(flat) if flat.numel() else b""
-        return [host[off[i]:off[i + 1]] for i in range(n_frames)]
+    def _compact_encode(self, profile, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True):
+        """The quantiser (profile 1: K7; profile 2: DCT, masking, TNS analysis) and the Exp-Golomb-Rice coder on the device
+        (profile1.py:15-45, profile2.py:15-52) -> (flat, offsets): the pre-deflate body of frame i at
+        ``flat[offsets[i]:offsets[i + 1]]``; the integers never leave the device."""
+        core = self.core
+        analogue, golomb = ((core.p1_analogue_batch, core.p1_golomb_encode_batch) if profile == 1 else
+                            (core.p2_analogue_batch, core.p2_golomb_encode_batch))
+        return golomb(*analogue(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level, frame_stride=hop, n_valid=n_valid,
+                                raw_be_ints=raw_be_ints))
 
-    def p2_encode_bodies(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
-        """``p1_encode_bodies`` for profile 2: DCT, masking, TNS analysis, quantiser and the three-stream Golomb coder on the
-        device (profile2.py:15-52), one D2H copy of exactly the body bytes."""
-        q, tq, lpc = self.core.p2_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
-                                                 frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
-        flat, offsets = self.core.p2_golomb_encode_batch(q, tq, lpc)
+    def _bodies_down(self, flat, offsets) -> list:
+        """one D2H copy of exactly the body bytes"""
         off = offsets.cpu().numpy()
         host = self._down_bytes(flat) if flat.numel() else b""
-        return [host[off[i]:off[i + 1]] for i in range(n_frames)]
+        return [host[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    # p{1,2}_encode_bodies: the pre-deflate bodies, the host deflates; p{1,2}_encode_payloads: the deflate on the device too
+    # (DESIGN.md 4g), the bodies stay there.  Arguments as _compact_encode's, without the profile.
+    def p1_encode_bodies(self, *args, **kw) -> list:
+        return self._bodies_down(*self._compact_encode(1, *args, **kw))
+
+    def p2_encode_bodies(self, *args, **kw) -> list:
+        return self._bodies_down(*self._compact_encode(2, *args, **kw))
+
+    def p1_encode_payloads(self, *args, **kw) -> list:
+        return self.deflate_payloads(*self._compact_encode(1, *args, **kw))
+
+    def p2_encode_payloads(self, *args, **kw) -> list:
+        return self.deflate_payloads(*self._compact_encode(2, *args, **kw))
 
     # ------------------------------------------------------------------ device deflate (Encoder(device_deflate=True))
     def deflate_payloads(self, flat, offsets) -> list:
@@ -186,76 +208,6 @@ class HipBridge:
         self.last_deflate_host = int(left.size)
         return pays
 
-    def p1_encode_payloads(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
-        """``p1_encode_bodies`` with the deflate on the device too: K7, the Exp-Golomb-Rice coder and zlib's raw deflate,
-        -> the deflated payload of every frame (profile1.py:15-50); the bodies stay on the device."""
-        q, tq = self.core.p1_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
-                                            frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
-        return self.deflate_payloads(*self.core.p1_golomb_encode_batch(q, tq))
-
-    def p2_encode_payloads(self, pcm: bytes, fmt, n_frames, N, C, bits, srate, loss_level, hop, n_valid, raw_be_ints=True) -> list:
-        """``p2_encode_bodies`` with the deflate on the device too (profile2.py:15-54)."""
-        q, tq, lpc = self.core.p2_analogue_batch(self._up(pcm), fmt, n_frames, N, C, bits, srate, loss_level,
-                                                 frame_stride=hop, n_valid=n_valid, raw_be_ints=raw_be_ints)
-        return self.deflate_payloads(*self.core.p2_golomb_encode_batch(q, tq, lpc))
-
-    def p1_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
-        """Inflated frame bodies -> PCM: Golomb decode (profile1.py:59-64) and K8 on the device, one H2D copy of the
-        bodies (about a byte per coefficient instead of the four of an int32 array)."""
-        t = self.torch
-        off = np.zeros(len(bodies) + 1, np.int64)
-        np.cumsum([len(b) for b in bodies], out=off[1:])
-        flat = self._up(b"".join(bodies) + bytes(8))              # the decoder reads the stream as aligned 32-bit words: tail slack (frad_hip.h)
-        q, tq, status = self.core.p1_golomb_decode_batch(flat, t.from_numpy(off).to(self.device), N, C)
-        return self.core.p1_digital_batch(q, tq, N, C, bits, srate).cpu().numpy()
-
-    def p1_decode_run(self, bodies: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
-        """A run of overlapped compact frames, whole on the device: Golomb decode, K8, the Hann cross-fade against
-        ``prev_tail`` (decoder.py:28-46) and -- with ``out_format`` -- the output conversion in the same pass.  One upload
-        of the inflated bodies, one download of the finished PCM ``[n_frames * cut, C]`` and of the new tail (float64)."""
-        from .backend.pcmformat import ff_format_to_numpy_type
-        t = self.torch
-        off = np.zeros(len(bodies) + 1, np.int64)
-        np.cumsum([len(b) for b in bodies], out=off[1:])
-        flat = self._up(b"".join(bodies) + bytes(8))
-        q, tq, status = self.core.p1_golomb_decode_batch(flat, t.from_numpy(off).to(self.device), N, C)
-        frames = self.core.p1_digital_batch(q, tq, N, C, bits, srate)
-        pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
-        out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
-        if out.dtype == t.uint8:
-            pcm = np.frombuffer(out.cpu().numpy().tobytes(), ff_format_to_numpy_type(out_format)).reshape(-1, C)
-        else:
-            pcm = out.cpu().numpy().reshape(-1, C)
-        return pcm, nxt.cpu().numpy()
-
-    def _p2_integers(self, bodies: list, N, C):
-        t = self.torch
-        off = np.zeros(len(bodies) + 1, np.int64)
-        np.cumsum([len(b) for b in bodies], out=off[1:])
-        flat = self._up(b"".join(bodies) + bytes(8))              # aligned 32-bit word reads: tail slack (frad_hip.h)
-        return self.core.p2_golomb_decode_batch(flat, t.from_numpy(off).to(self.device), N, C)
-
-    def p2_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
-        """Inflated profile-2 bodies -> PCM [n_frames, N, C] (profile2.py:64-91): Golomb decode, TNS synthesis and the
-        threshold ramp (frad_p2_synth), inverse DCT (frad_p0_digital); one upload of the bodies, one download."""
-        q, tq, lpc, _ = self._p2_integers(bodies, N, C)
-        return self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate).cpu().numpy()
-
-    def p2_decode_run(self, bodies: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
-        """``p1_decode_run`` for profile 2: the run of overlapped frames whole on the device, through the cross-fade and
-        the optional output conversion.  -> (PCM [n_frames * cut, C], new tail float64)"""
-        from .backend.pcmformat import ff_format_to_numpy_type
-        t = self.torch
-        q, tq, lpc, _ = self._p2_integers(bodies, N, C)
-        frames = self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate)
-        pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
-        out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
-        if out.dtype == t.uint8:
-            pcm = np.frombuffer(out.cpu().numpy().tobytes(), ff_format_to_numpy_type(out_format)).reshape(-1, C)
-        else:
-            pcm = out.cpu().numpy().reshape(-1, C)
-        return pcm, nxt.cpu().numpy()
-
     # ------------------------------------------------------------------ device inflate (Decoder(device_inflate=True))
     def inflate_run(self, payloads: list, profile: int, N, C):
         """The deflated payloads of a compact run -> their inflated bodies on the device, compacted: (bodies uint8 with the 8
@@ -281,6 +233,15 @@ class HipBridge:
                 lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, bodies.data_ptr(), offsets.data_ptr(), core._stream_ptr())
         return bodies, offsets
 
+    # ------------------------------------------------------------------ the compact decode chain: source, frames, sink
+    def _bodies_up(self, bodies: list):
+        """inflated bodies -> (flat uint8, offsets int64 [n + 1]) on the device: one upload of the bytes (about a byte per
+        coefficient instead of the four of an int32 array) with the tail slack of ``inflate_run``'s"""
+        off = np.zeros(len(bodies) + 1, np.int64)
+        np.cumsum([len(b) for b in bodies], out=off[1:])
+        flat = self._up(b"".join(bodies) + bytes(8))              # the decoder reads the stream as aligned 32-bit words (frad_hip.h)
+        return flat, self.torch.from_numpy(off).to(self.device)
+
     def _frames_dev(self, profile, bodies, offsets, N, C, bits, srate):
         """inflated bodies on the device -> float64 frames [n, N, C] on the device (Golomb decode, K8 / p2 synthesis)"""
         if profile == 1:
@@ -289,63 +250,54 @@ class HipBridge:
         q, tq, lpc, _ = self.core.p2_golomb_decode_batch(bodies, offsets, N, C)
         return self.core.p2_digital_batch(q, tq, lpc, N, C, bits, srate)
 
-    def decode_bodies_deflated(self, profile, payloads: list, N, C, bits, srate):
-        """``p{1,2}_decode_bodies`` from the deflated payloads, inflated on the device; None when a frame does not inflate."""
-        got = self.inflate_run(payloads, profile, N, C)
-        if got is None:
-            return None
-        return self._frames_dev(profile, *got, N, C, bits, srate).cpu().numpy()
+    def _p2_integers(self, bodies: list, N, C):
+        """inflated profile-2 bodies -> the coder's integers on the device, before the synthesis (tests/test_p2_decode.py)"""
+        return self.core.p2_golomb_decode_batch(*self._bodies_up(bodies), N, C)
 
-    def decode_run_deflated(self, profile, payloads: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
-        """``p{1,2}_decode_run`` from the deflated payloads: inflate, Golomb decode, K8 / p2 synthesis, the cross-fade and the
-        optional output conversion, all on the device -> (PCM [n * cut, C], new tail float64); None when a frame does not
-        inflate."""
-        from .backend.pcmformat import ff_format_to_numpy_type
+    def _crossfade(self, frames, ratio, prev_tail, out_format=None):
+        """frames on the device through the Hann cross-fade against ``prev_tail`` (decoder.py:28-46) and -- with
+        ``out_format`` -- the output conversion in the same pass -> (PCM, new tail float64) on the host"""
         t = self.torch
-        got = self.inflate_run(payloads, profile, N, C)
-        if got is None:
-            return None
-        frames = self._frames_dev(profile, *got, N, C, bits, srate)
         pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
         out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
+        pcm = out.cpu().numpy()
         if out.dtype == t.uint8:
-            pcm = np.frombuffer(out.cpu().numpy().tobytes(), ff_format_to_numpy_type(out_format)).reshape(-1, C)
-        else:
-            pcm = out.cpu().numpy().reshape(-1, C)
+            from .backend.pcmformat import ff_format_to_numpy_type
+            pcm = np.frombuffer(pcm.tobytes(), ff_format_to_numpy_type(out_format))
         return pcm, nxt.cpu().numpy()
 
-    # ------------------------------------------------------------------ group-level helpers of decode_batch (batch.py)
-    # The frames of every stream of a group go through each stage in one call; what comes back stays on the device until
-    # clips_overlap_add has assembled the ragged output.
-    def compact_frames_dev(self, profile, bodies: list, N, C, bits, srate):
-        """inflated bodies of any number of streams -> float64 frames [n, N, C] on the device: one upload, one Golomb decode,
-        one K8 / p2 synthesis + inverse DCT (an empty body is a frame of zeros, profile1.py:59-60)"""
-        t = self.torch
-        off = np.zeros(len(bodies) + 1, np.int64)
-        np.cumsum([len(b) for b in bodies], out=off[1:])
-        flat = self._up(b"".join(bodies) + bytes(8))              # aligned 32-bit word reads: tail slack (frad_hip.h)
-        return self._frames_dev(profile, flat, t.from_numpy(off).to(self.device), N, C, bits, srate)
-
-    def deflated_frames_dev(self, profile, payloads: list, N, C, bits, srate):
-        """``compact_frames_dev`` from the deflated payloads, inflated on the device; None when a frame does not inflate"""
-        got = self.inflate_run(payloads, profile, N, C)
-        if got is None:
+    def compact_decode(self, profile, items: list, N, C, bits, srate, deflated=False, run=None, keep=False):
+        """Profile-1 / profile-2 frames of any number of streams, every stage in one call.  Source: the inflated bodies
+        (an empty one is a frame of zeros, profile1.py:59-60), or -- ``deflated`` -- the payloads as they are, inflated on the
+        device; None then when a frame does not inflate.  Golomb decode, K8 / p2 synthesis + inverse DCT.  Sink: the frames
+        float64 [n, N, C], downloaded or -- ``keep`` -- left on the device; with ``run`` = (ratio, prev_tail, out_format)
+        the run of overlapped frames goes on through the cross-fade -> (PCM [n * cut, C], new tail float64).  One upload,
+        one chain, one download."""
+        src = self.inflate_run(items, profile, N, C) if deflated else self._bodies_up(items)
+        if src is None:
             return None
-        return self._frames_dev(profile, *got, N, C, bits, srate)
+        frames = self._frames_dev(profile, *src, N, C, bits, srate)
+        if run is not None:
+            pcm, tail = self._crossfade(frames, *run)
+            return pcm.reshape(-1, C), tail
+        return frames if keep else frames.cpu().numpy()
 
-    def lossless_frames_dev(self, profile, payloads: list, N, C, bits, little_endian):
-        """equally long profile-0 / 4 payloads -> float64 frames [n, N, C] on the device: one upload, one launch"""
-        n, nb = len(payloads), len(payloads[0])
-        stride = (nb + 15) // 16 * 16
-        host = np.zeros((n, stride), np.uint8)
-        host[:, :nb] = np.frombuffer(b"".join(payloads), np.uint8).reshape(n, nb)
-        dev = self.torch.from_numpy(host).to(self.device)
-        return self.core.digital_batch(profile, dev, n, N, C, bits, little_endian)
+    def p1_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
+        return self.compact_decode(1, bodies, N, C, bits, srate)
+
+    def p2_decode_bodies(self, bodies: list, N, C, bits, srate) -> np.ndarray:
+        return self.compact_decode(2, bodies, N, C, bits, srate)
+
+    def p1_decode_run(self, bodies: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
+        return self.compact_decode(1, bodies, N, C, bits, srate, run=(ratio, prev_tail, out_format))
+
+    def p2_decode_run(self, bodies: list, N, C, bits, srate, ratio, prev_tail, out_format=None):
+        return self.compact_decode(2, bodies, N, C, bits, srate, run=(ratio, prev_tail, out_format))
 
     def clips_overlap_add(self, frames, clip_frame0, N, C, ratio, tails: list, tail_off, tail_rows, out_format=None, tail_win=None,
                           as_tensor=False):
         """The clips' cross-fade, concatenation and output conversion in one launch (core.clips_overlap_add).  ``frames``: a
-        device tensor from the helpers above (or an ndarray), ``tails``: the last-frame tensors, concatenated here in the order
+        device tensor (``keep``) from compact_decode / lossless_decode, or an ndarray, ``tails``: the last-frame tensors, concatenated here in the order
         ``tail_off`` counts them.  -> (out, out_off): a device tensor with ``as_tensor``, else one download into an ndarray
         [rows, C] of float64 or of ``out_format``'s dtype."""
         from .backend.pcmformat import ff_format_to_numpy_type
@@ -369,10 +321,7 @@ class HipBridge:
                                           N, C, bits, srate).cpu().numpy()
 
     def overlap_add(self, frames: np.ndarray, ratio: int, prev_tail):
-        t = self.torch
-        pt = t.from_numpy(np.ascontiguousarray(prev_tail)).to(self.device) if prev_tail is not None else None
-        out, nxt = self.core.p1_overlap_add(t.from_numpy(np.ascontiguousarray(frames)).to(self.device), ratio, pt)
-        return out.cpu().numpy(), nxt.cpu().numpy()
+        return self._crossfade(self.torch.from_numpy(np.ascontiguousarray(frames)).to(self.device), ratio, prev_tail)
 
     # ------------------------------------------------------------------ Reed-Solomon (csrc/frad_ecc.hip)
     def _rs_upload(self, payloads, dsize, codesize, repair):

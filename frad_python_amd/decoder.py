@@ -5,21 +5,13 @@ decoded by ONE launch of the HIP transform core (the reference decodes one frame
 decoder.py:55-80), and the compact profiles' Hann cross-fade runs on the device as well."""
 from __future__ import annotations
 
-import struct
-import zlib
-
 import numpy as np
 
-from . import common, ecc
-from .fourier import profiles
+from . import common
+from .fourier import BIT_DEPTHS, profiles
+from .frames import DEFLATED, Damaged, classify, inflate_bodies, repair
 from .tools.asfh import ASFH
 from .backend.pcmformat import from_f64
-
-_LOSSLESS_DEPTHS = (12, 16, 24, 32, 48, 64)
-_P1_DEPTHS = (8, 12, 16, 24, 32, 48, 64)
-_P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)                 # fourier/profile2.py:7
-_DEFLATED = (1, 2)                                      # compact profiles: deflated Golomb bodies, cut from the stream
-_BUILT = (0, 1, 2, 4)
 
 
 class DecodeResult:
@@ -33,30 +25,25 @@ class DecodeResult:
         self.crit = crit
 
 
-def _lossless_frame_len(nbytes: int, depth_idx: int, channels: int, header_fsize: int) -> int:
-    """Sample-frames a lossless payload holds.  The reference's profile0/4.digital never look at the header's fsize: they
-    unpack every stored value and reshape(-1, channels) (profile0.py:46-69, profile4.py:43-63), so the payload length
-    decides.  A length that is no whole number of sample-frames (the reference's reshape then raises) keeps the header
-    value and fails in the launch checks."""
-    bits = _LOSSLESS_DEPTHS[depth_idx] if depth_idx < len(_LOSSLESS_DEPTHS) else 0
-    if not bits or channels < 1:
-        return header_fsize
-    values = (nbytes * 2) // 3 if bits == 12 else (nbytes * 8) // bits
-    return values // channels if values and values % channels == 0 else header_fsize
+class _Runs:
+    """The frames of one process() call, gathered into runs: consecutive frames of one key -- and, for the lossless
+    profiles, one payload length -- are decoded together when the run breaks or the call ends.  Both parsers push here."""
 
+    def __init__(self, decode):
+        self.decode, self.pieces, self.frames = decode, [], 0
+        self.key, self.run = None, []
 
-def _strip_ecc(frad: bytes, dsize: int, codesize: int) -> bytes:
-    """tools/ecc.py:14-25 with repair off: drop the Reed-Solomon code bytes of every block."""
-    block = dsize + codesize
-    return b"".join(frad[i:i + block][:max(len(frad[i:i + block]) - codesize, 0)] for i in range(0, len(frad), block))
+    def push(self, key, entry):
+        if key != self.key or (key[0] not in DEFLATED and self.run and entry[2] != self.run[0][2]):
+            self.close()
+            self.key = key
+        self.run.append(entry)
+        self.frames += 1
 
-
-class _Damaged:
-    """An ECC payload whose checksum fails, waiting for the batched repair of its run (frad_rs_repair)."""
-    __slots__ = ("frad", "dsize", "codesize")
-
-    def __init__(self, frad: bytes, dsize: int, codesize: int):
-        self.frad, self.dsize, self.codesize = frad, dsize, codesize
+    def close(self):
+        if self.run:
+            self.pieces.extend(self.decode(self.key, self.run))
+        self.key, self.run = None, []
 
 
 class Decoder:
@@ -105,99 +92,69 @@ class Decoder:
         """entries: (payload bytes or None, offset in self._data, length) per frame of the run"""
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
         entries = self._repair(entries)
+        bits = BIT_DEPTHS[profile][depth_idx]
         strided = getattr(self.bridge, "lossless_decode_strided", None)
-        if (profile not in _DEFLATED and strided is not None and len(entries) > 1 and all(e[0] is None for e in entries)):
+        if (profile not in DEFLATED and strided is not None and len(entries) > 1 and all(e[0] is None for e in entries)):
             step = entries[1][1] - entries[0][1]
             if step > 0 and all(entries[i + 1][1] - entries[i][1] == step for i in range(len(entries) - 1)):
                 first, nb = entries[0][1], entries[0][2]
                 region = memoryview(self._data)[first:entries[-1][1] + nb]
                 narrow = self.out_format if not self.overlap_fragment.size else None
                 if narrow is not None:
-                    pcm = strided(profile, region, len(entries), step, nb, fsize, channels, _LOSSLESS_DEPTHS[depth_idx], endian, out_format=narrow)
+                    pcm = strided(profile, region, len(entries), step, nb, fsize, channels, bits, endian, out_format=narrow)
                 else:
-                    pcm = strided(profile, region, len(entries), step, nb, fsize, channels, _LOSSLESS_DEPTHS[depth_idx], endian)
+                    pcm = strided(profile, region, len(entries), step, nb, fsize, channels, bits, endian)
                 if pcm is not None:
                     if self.overlap_fragment.size:
                         return self._overlap_host(pcm, key)
                     return [pcm.reshape(-1, channels)]             # one piece: no per-frame list, no concatenate
         payloads = [e[0] if e[0] is not None else self._data[e[1]:e[1] + e[2]] for e in entries]
-        if profile in _DEFLATED and self.device_inflate:
-            got = self._decode_run_device_inflate(key, payloads)
-            if got is not None:
-                return got
-        if profile in _DEFLATED:
-            bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth_idx]
-            # inflate on the host (profile1.py:59, profile2.py:61); Golomb decode + dequantise (+ TNS) + IDCT behind the bridge
-            # (on the device)
-            def inflate(frad):
-                try:
-                    return zlib.decompress(frad, wbits=-15)
-                except Exception:
-                    return None                                      # profile1.py:59-60, profile2.py:63-64 -> a frame of zeros
-            from .encoder import _map_zlib
-            bodies = _map_zlib(inflate, payloads)                  # runs of frames per pool task
-            bad = [i for i, b in enumerate(bodies) if b is None]
-            bodies = [b if b is not None else b"" for b in bodies]
-            fused = getattr(self.bridge, "p1_decode_run" if profile == 1 else "p2_decode_run", None)
-            L = fsize - fsize * (ratio - 1) // ratio if ratio else 0
-            if fused is not None and ratio != 0 and (not self.overlap_fragment.size or self.overlap_fragment.shape == (L, channels)):
-                # the whole run on the device: Golomb decode, K8, the cross-fade and the output conversion; an undecodable frame
-                # is an empty body = all-zero integers = a frame of zeros (profile1.py:59-60) before the cross-fade, as in the reference
-                prev = self.overlap_fragment if self.overlap_fragment.size else None
-                pcm, self.overlap_fragment = fused(bodies, fsize, channels, bits, srate, ratio, prev, self.out_format)
-                return [pcm]
-            pcm = (self.bridge.p1_decode_bodies if profile == 1 else self.bridge.p2_decode_bodies)(bodies, fsize, channels, bits, srate)
-            for i in bad:
-                pcm[i] = 0.0
-        else:
-            pcm = self.bridge.lossless_decode(profile, payloads, fsize, channels, _LOSSLESS_DEPTHS[depth_idx], endian)
+        if profile in DEFLATED:
+            on_device = self.device_inflate and getattr(self.bridge, "compact_decode", None) is not None
+            return self._decode_compact(key, payloads, on_device)
+        pcm = self.bridge.lossless_decode(profile, payloads, fsize, channels, bits, endian)
         return self._finish_run(pcm, key)
 
-    def _decode_run_device_inflate(self, key, payloads: list):
-        """device_inflate=True: the run's deflated payloads go to the device as they are (frad_inflate_raw, then the same
-        chain as the host-inflate path takes).  None when a frame does not inflate there: the caller's host path then decodes
-        the whole run, which keeps a frame zlib rejects a frame of zeros (profile1.py:59-60, profile2.py:63-64)."""
+    def _decode_compact(self, key, payloads: list, on_device: bool) -> list:
+        """A run of profile-1 / profile-2 frames.  The bodies come from the host inflate (profile1.py:59, profile2.py:61), or
+        -- ``on_device``: device_inflate=True on a bridge that has it -- the deflated payloads go to the device as they are
+        (frad_inflate_raw).  Golomb decode, dequantiser (+ TNS) and IDCT run behind the bridge either way; the whole run stays
+        there through the cross-fade and the output conversion when the pending fragment fits."""
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
-        if getattr(self.bridge, "decode_run_deflated", None) is None:
-            return None                                              # a bridge without a device inflate (CPU-only tests)
-        bits = (_P1_DEPTHS if profile == 1 else _P2_DEPTHS)[depth_idx]
+        br, bits = self.bridge, BIT_DEPTHS[profile][depth_idx]
+        bodies, bad = (payloads, []) if on_device else inflate_bodies(payloads)
+        fused = on_device or getattr(br, f"p{profile}_decode_run", None) is not None
         L = fsize - fsize * (ratio - 1) // ratio if ratio else 0
-        if ratio != 0 and (not self.overlap_fragment.size or self.overlap_fragment.shape == (L, channels)):
-            prev = self.overlap_fragment if self.overlap_fragment.size else None
-            got = self.bridge.decode_run_deflated(profile, payloads, fsize, channels, bits, srate, ratio, prev, self.out_format)
+        run = None
+        if fused and ratio != 0 and (not self.overlap_fragment.size or self.overlap_fragment.shape == (L, channels)):
+            # an undecodable frame is an empty body = all-zero integers = a frame of zeros (profile1.py:59-60) before the
+            # cross-fade, as in the reference
+            run = (ratio, self.overlap_fragment if self.overlap_fragment.size else None, self.out_format)
+        if on_device:
+            got = br.compact_decode(profile, bodies, fsize, channels, bits, srate, deflated=True, run=run)
             if got is None:
-                return None
+                # a frame does not inflate there: the host inflate decodes the whole run, which keeps a frame zlib rejects a
+                # frame of zeros (profile1.py:59-60, profile2.py:63-64)
+                return self._decode_compact(key, payloads, False)
+        elif run is not None:
+            got = getattr(br, f"p{profile}_decode_run")(bodies, fsize, channels, bits, srate, *run)
+        else:
+            got = getattr(br, f"p{profile}_decode_bodies")(bodies, fsize, channels, bits, srate)
+        if run is not None:
             pcm, self.overlap_fragment = got
             return [pcm]
-        pcm = self.bridge.decode_bodies_deflated(profile, payloads, fsize, channels, bits, srate)
-        if pcm is None:
-            return None
-        return self._finish_run(pcm, key)
+        for i in bad:
+            got[i] = 0.0
+        return self._finish_run(got, key)
 
     def _repair(self, entries: list) -> list:
-        """Replace the run's damaged payloads by their repaired data parts: one frad_rs_repair batch per stored ratio."""
-        groups = {}
-        for i, e in enumerate(entries):
-            if isinstance(e[0], _Damaged):
-                groups.setdefault((e[0].dsize, e[0].codesize), []).append(i)
-        if not groups:
+        """Replace the run's damaged payloads by their repaired data parts (frames.repair)."""
+        if not any(isinstance(e[0], Damaged) for e in entries):
             return entries
-        entries = list(entries)
-        for (dsize, csize), idx in groups.items():
-            if not 1 <= dsize + csize <= 255:
-                raise ValueError(f"Reed-Solomon blocks of {dsize} + {csize} bytes cannot be decoded")
-            fixed, _, _ = self.bridge.rs_repair([entries[i][0].frad for i in idx], dsize, csize)
-            for i, f in zip(idx, fixed):
-                entries[i] = (f, entries[i][1], entries[i][2])
-        return entries
-
-    def _unprotect(self, frad: bytes, profile: int, dsize: int, csize: int, crc: int):
-        """ecc.decode (decoder.py:63-68): strip the check bytes, or -- fix_error and a failing checksum -- mark the payload
-        for repair.  -> (payload or _Damaged, data bytes)"""
-        if self.fix_error and ecc.needs_repair(profile, frad, crc):
-            return _Damaged(frad, dsize, csize), ecc.data_len(len(frad), dsize, csize)
-        frad = _strip_ecc(frad, dsize, csize)
-        return frad, len(frad)
+        for p, _, _ in entries:
+            if isinstance(p, Damaged) and not 1 <= p.dsize + p.codesize <= 255:
+                raise ValueError(f"Reed-Solomon blocks of {p.dsize} + {p.codesize} bytes cannot be decoded")
+        return [(f, e[1], e[2]) for f, e in zip(repair(self.bridge, [e[0] for e in entries]), entries)]
 
     def _finish_run(self, pcm: np.ndarray, key) -> list:
         profile, fsize, channels, depth_idx, endian, srate, ratio = key
@@ -261,28 +218,35 @@ class Decoder:
 
     def _take_frame(self, stream_was_empty: bool):
         """Cut the payload of the header just completed; None while it is still arriving."""
-        need = self.asfh.frmbytes
+        a, off = self.asfh, self._pos
         self.broken_frame = False
-        if len(self._data) - self._pos < need:
+        if len(self._data) - off < a.frmbytes:
             self.broken_frame = stream_was_empty                # process(b'') marks a truncated frame (decoder.py:58-60)
             return None
-        off = self._pos
-        self._pos += need
-        a = self.asfh
-        if a.profile not in _BUILT:
-            raise NotImplementedError(f"profile {a.profile} is not built (upstream: in development)")
-        # lossless payloads stay where they are in the stream (offset, length): a run of equally spaced frames goes to
-        # the device as one strided buffer; everything else is cut out here
-        frad, nb = None, need
-        if a.profile in _DEFLATED or a.ecc:
-            frad = self._data[off:off + need]
-            nb = len(frad)
-            if a.ecc:
-                frad, nb = self._unprotect(frad, a.profile, a.ecc_dsize, a.ecc_codesize, int.from_bytes(a.crc, "big"))
-        fsize = a.fsize if a.profile in _DEFLATED else _lossless_frame_len(nb, a.bit_depth_index, a.channels, a.fsize)
-        key = (a.profile, fsize, a.channels, a.bit_depth_index, a.endian, a.srate, a.overlap_ratio)
+        self._pos += a.frmbytes
+        got = classify(self._data, (0, off, a.frmbytes, a.profile, a.ecc, a.endian, a.bit_depth_index, a.channels, a.srate, a.fsize,
+                                    a.overlap_ratio, a.ecc_dsize, a.ecc_codesize, False, int.from_bytes(a.crc, "big")), self.fix_error)
         a.clear()
-        return key, (frad, off, nb)
+        return got
+
+    def _take_header(self) -> str:
+        """The byte-wise parser, the reference's algorithm (decoder.py:82-98), up to the end of the next header.  Returns
+        'header' (complete: its payload is next), 'end' (no signature, or the header is still arriving), 'flush' or 'crit'."""
+        if not self._lock_on_signature():
+            return "end"
+        state = self._read_header()
+        if state == "Incomplete":
+            return "end"
+        if state == "ForceFlush":
+            return "flush"
+        return "crit" if not self.asfh.criteq(self.info) and self._crit() else "header"
+
+    def _crit(self) -> bool:
+        """The header in self.asfh differs from the last one in channel count or sample rate (decoder.py:93-98): True when
+        that ends the call.  ``info`` IS ``asfh`` from here on, as in the reference, so this fires for the first header only."""
+        previous = (self.info.srate, self.info.channels)
+        self.info, self._crit_srate = self.asfh, previous[0]
+        return any(previous)
 
     def process(self, stream: bytes) -> DecodeResult:
         """Parse as the reference does (decoder.py:51-108) but decode runs of like frames in one launch each."""
@@ -302,62 +266,27 @@ class Decoder:
         return res
 
     def _process(self, stream_was_empty: bool) -> DecodeResult:
-        pieces, frames = [], 0
-        run_key, run = None, []
-
-        def close_run():
-            nonlocal run_key, run
-            if run:
-                pieces.extend(self._decode_run(run_key, run))
-            run_key, run = None, []
-
+        runs = _Runs(self._decode_run)
         while True:
             if self.asfh.all_set:
                 got = self._take_frame(stream_was_empty)
                 if got is None:
+                    stop = "end"
                     break
-                key, frad = got
-                if key != run_key or (key[0] not in _DEFLATED and run and frad[2] != run[0][2]):
-                    close_run()
-                    run_key = key
-                run.append(frad)
-                frames += 1
-                continue
-            if not self.asfh.buffer and self._scan is not None:
-                # steady state (no half-read header carried over): the native scanner (frad_asfh_scan) lists every
-                # complete frame ahead in one pass; whatever it cannot finish is left to the byte-wise parser below
-                stop = self._take_scanned(pieces, close_run, lambda k, e: self._append(k, e))
-                frames += self._scanned_frames
-                run_key, run = self._run_key, self._run
-                if stop == "flush":
-                    close_run()
-                    pieces.append(self.flush().pcm)
-                    break
-                if stop == "crit":
-                    close_run()
-                    pieces.append(self.flush().pcm)
-                    return DecodeResult(pieces, self._crit_srate, frames, True)
-                if stop == "end":
-                    break
-                # "partial": fall through, the byte-wise parser takes the unfinished header / payload
-            if not self._lock_on_signature():
+                runs.push(*got)         # joins the scanned frames behind it: both kinds of entry are offsets into self._data
+            # steady state (no half-read header carried over): the native scanner (frad_asfh_scan) lists every complete
+            # frame ahead in one pass; whatever it cannot finish ('partial') is left to the byte-wise parser
+            stop = self._take_scanned(runs) if not self.asfh.buffer and self._scan is not None else "partial"
+            if stop == "partial":
+                stop = self._take_header()
+            if stop != "header":
                 break
-            state = self._read_header()
-            if state == "Incomplete":
-                break
-            if state == "ForceFlush":
-                close_run()
-                pieces.append(self.flush().pcm)
-                break
-            if not self.asfh.criteq(self.info):                 # channel count or sample rate changed
-                previous = (self.info.srate, self.info.channels)
-                self.info = self.asfh
-                if any(previous):
-                    close_run()
-                    pieces.append(self.flush().pcm)
-                    return DecodeResult(pieces, previous[0], frames, True)
-        close_run()
-        return DecodeResult(pieces, self.asfh.srate, frames, False)
+        runs.close()
+        if stop in ("flush", "crit"):
+            runs.pieces.append(self.flush().pcm)
+        if stop == "crit":
+            return DecodeResult(runs.pieces, self._crit_srate, runs.frames, True)
+        return DecodeResult(runs.pieces, self.asfh.srate, runs.frames, False)
 
     # ------------------------------------------------------------------ table-driven parsing (native scanner)
     @property
@@ -367,48 +296,24 @@ class Decoder:
         lib = getattr(self.bridge, "scan_lib", None)
         return lib.asfh_scan if lib is not None else None
 
-    def _append(self, key, entry):
-        if key != self._run_key or (key[0] not in _DEFLATED and self._run and entry[2] != self._run[0][2]):
-            if self._run:
-                self._pieces.extend(self._decode_run(self._run_key, self._run))
-            self._run_key, self._run = key, []
-        self._run.append(entry)
-
-    def _take_scanned(self, pieces, close_run, append) -> str:
+    def _take_scanned(self, runs: _Runs) -> str:
         """Consume the frames the scanner found from self._pos on.  Returns why it stopped: 'end' (nothing more in the
         buffer), 'partial' (an unfinished header or payload follows at self._pos), 'flush' (a force-flush header was
         consumed) or 'crit' (channels / rate changed, decoder.py:93-98)."""
-        self._pieces, self._scanned_frames = pieces, 0
-        close_run()
-        self._run_key, self._run = None, []
         table, next_pos, why = self._scan(self._data, self._pos)
-        a = self.asfh
-        rows = table.tolist()
-        for (h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc) in rows:
+        a, data, fix_error = self.asfh, self._data, self.fix_error
+        for row in table.tolist():
+            h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc = row
             a.profile, a.ecc, a.endian, a.bit_depth_index = profile, bool(is_ecc), bool(le), depth
             a.channels, a.srate, a.fsize, a.frmbytes = ch, srate, fsize, p_len
             if fflush:
                 self._pos = p_off
                 return "flush"
             a.overlap_ratio, a.ecc_dsize, a.ecc_codesize = ratio, dsize, csize
-            if not a.criteq(self.info):
-                previous = (self.info.srate, self.info.channels)
-                self.info = a
-                if any(previous):
-                    self._pos, self._crit_srate = p_off, previous[0]
-                    return "crit"
-            if profile not in _BUILT:
-                raise NotImplementedError(f"profile {profile} is not built (upstream: in development)")
-            frad, nb = None, p_len
-            if profile in _DEFLATED or is_ecc:
-                frad = self._data[p_off:p_off + p_len]
-                nb = len(frad)
-                if is_ecc:
-                    frad, nb = self._unprotect(frad, profile, dsize, csize, crc)
-            n_eff = fsize if profile in _DEFLATED else _lossless_frame_len(nb, depth, ch, fsize)
-            key = (profile, n_eff, ch, depth, bool(le), srate, ratio)
-            append(key, (frad, p_off, nb))
-            self._scanned_frames += 1
+            if not a.criteq(self.info) and self._crit():
+                self._pos = p_off
+                return "crit"
+            runs.push(*classify(data, row, fix_error))
             self._pos = p_off + p_len
             self.broken_frame = False
         if why == 0:                                            # FRAD_SCAN_END: keep a possibly split signature

@@ -13,35 +13,8 @@ import numpy as np
 from .backend.pcmformat import ff_format_to_numpy_type
 from .fourier import AVAILABLE, BIT_DEPTHS, SEGMAX, profiles
 from .fourier.profiles import compact
+from .frames import map_zlib
 from .tools.asfh import ASFH
-
-_LOSSLESS_DEPTHS = (12, 16, 24, 32, 48, 64)
-_P1_DEPTHS = (8, 12, 16, 24, 32, 48, 64)
-_P2_DEPTHS = (8, 10, 12, 14, 16, 20, 24)        # fourier/profile2.py:7
-
-
-_POOL = None
-
-
-def _map_zlib(fn, items: list) -> list:
-    """deflate / inflate of a batch's frames on a small thread pool: zlib releases the GIL, the frames are independent and
-    the results are the bytes the serial loop would give (profile1.py:50, :59).  Work is handed out in runs of frames so
-    that the pool's per-task overhead (tens of microseconds) does not exceed a frame's own cost."""
-    global _POOL
-    n = len(items)
-    if n < 32:
-        return [fn(b) for b in items]
-    if _POOL is None:
-        import os
-        from concurrent.futures import ThreadPoolExecutor
-        _POOL = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4))
-    workers = _POOL._max_workers
-    run = max(8, -(-n // (4 * workers)))
-    chunks = [items[i:i + run] for i in range(0, n, run)]
-    out = []
-    for part in _POOL.map(lambda ch: [fn(b) for b in ch], chunks):
-        out.extend(part)
-    return out
 
 
 class EncodeResult:
@@ -119,38 +92,30 @@ class Encoder:
         """n_frames frames of n_eff sample-frames, frame i starting i*hop sample-frames into `pcm`."""
         prof, C = self.asfh.profile, self.channels
         out = []
-        if prof == 2:
-            bits = self.bit_depth if self.bit_depth in _P2_DEPTHS else 16                    # profile2.py:16
+        depths = BIT_DEPTHS[prof]
+        if prof in profiles.COMPACT:
+            bits = self.bit_depth if self.bit_depth in depths else 16                        # profile1.py:16, profile2.py:16
             N = compact.get_samples_min_ge(n_eff)
-            # DCT, masking, TNS analysis, quantiser and the three Golomb streams on the device; the host deflates and frames
+            # the quantiser (profile 2: with masking and TNS analysis) and the Exp-Golomb-Rice coder behind the bridge (on the
+            # device); the host only deflates (profile1.py:50, profile2.py:54) and frames
             args = (pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate), self.loss_level, hop, n_valid)
             if self.device_deflate:
-                payloads = self.bridge.p2_encode_payloads(*args)            # ... and the deflate as well (DESIGN.md 4g)
+                payloads = getattr(self.bridge, f"p{prof}_encode_payloads")(*args)   # ... and the deflate as well (DESIGN.md 4g)
             else:
-                payloads = _map_zlib(self._deflate, self.bridge.p2_encode_bodies(*args))
-            out += self._emit_all([(frad, _P2_DEPTHS.index(bits), n_valid) for frad in payloads])
-        elif prof == 1:
-            bits = self.bit_depth if self.bit_depth in _P1_DEPTHS else 16
-            N = compact.get_samples_min_ge(n_eff)
-            # quantiser and Exp-Golomb-Rice coder behind the bridge (on the device); the host only deflates (profile1.py:50) and frames
-            args = (pcm, self.pcm_format_name, n_frames, N, C, bits, compact.get_valid_srate(self.srate), self.loss_level, hop, n_valid)
-            if self.device_deflate:
-                payloads = self.bridge.p1_encode_payloads(*args)            # ... and the deflate as well (DESIGN.md 4g)
-            else:
-                payloads = _map_zlib(self._deflate, self.bridge.p1_encode_bodies(*args))
-            out += self._emit_all([(frad, _P1_DEPTHS.index(bits), n_valid) for frad in payloads])
+                payloads = map_zlib(self._deflate, getattr(self.bridge, f"p{prof}_encode_bodies")(*args))
+            out += self._emit_all([(frad, depths.index(bits), n_valid) for frad in payloads])
         else:
-            bits = self.bit_depth if self.bit_depth in _LOSSLESS_DEPTHS else 16
+            bits = self.bit_depth if self.bit_depth in depths else 16
             whole = getattr(self.bridge, "lossless_encode_stream", None)
             if whole is not None and n_frames > 1 and (not self.asfh.ecc or self.allow_ecc):
                 # headers, Reed-Solomon and checksums on the device, one copy back (bridge.py); falls through when a frame escalates
                 a = self.asfh
-                a.bit_depth_index, a.channels, a.fsize, a.srate = _LOSSLESS_DEPTHS.index(bits), C, n_eff, self.srate
+                a.bit_depth_index, a.channels, a.fsize, a.srate = depths.index(bits), C, n_eff, self.srate
                 ecc_kw = {"ecc_ratio": (a.ecc_dsize, a.ecc_codesize)} if a.ecc else {}
                 got = whole(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, a.endian, a.lossless_head, **ecc_kw)
                 if got is not None:
                     return got
-            out += self._emit_all([(frad, _LOSSLESS_DEPTHS.index(used), n_eff) for frad, used in
+            out += self._emit_all([(frad, depths.index(used), n_eff) for frad, used in
                                    self.bridge.lossless_encode(prof, pcm, self.pcm_format_name, n_frames, n_eff, C, bits, self.asfh.endian)])
         return b"".join(out)
 

@@ -7,8 +7,8 @@ frad_crc32_frames).  A stream written without ECC comes out as the reference enc
 from __future__ import annotations
 
 from . import common, ecc
-from .decoder import _strip_ecc
 from .fourier import profiles
+from .frames import repair, unprotect
 from .tools.asfh import ASFH
 
 
@@ -74,22 +74,13 @@ class Repairer:
         return a
 
     def _protect(self, data: bytes, rows: list) -> list:
-        br = self.bridge
-        payloads, damaged = [], {}
-        for i, (h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc) in enumerate(rows):
+        payloads = []
+        for h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, dsize, csize, fflush, crc in rows:
             frad = data[p_off:p_off + p_len]
-            if is_ecc:
-                if ecc.needs_repair(profile, frad, crc):
-                    damaged.setdefault((dsize, csize), []).append(i)
-                else:
-                    frad = _strip_ecc(frad, dsize, csize)
-            payloads.append(frad)
-        for (dsize, csize), idx in damaged.items():                 # ecc.decode with repair: one batch per stored ratio
-            fixed, _, _ = br.rs_repair([payloads[i] for i in idx], dsize, csize)
-            for i, f in zip(idx, fixed):
-                payloads[i] = f
+            payloads.append(unprotect(frad, profile, dsize, csize, crc, True)[0] if is_ecc else frad)
+        payloads = repair(self.bridge, payloads)                    # ecc.decode with repair: one batch per stored ratio
         dsize, csize = self.ecc_ratio
-        prot, crcs = br.rs_encode(payloads, dsize, csize, crc32=True)
+        prot, crcs = self.bridge.rs_encode(payloads, dsize, csize, crc32=True)
         out = []
         for row, frad, c in zip(rows, prot, crcs):
             h_off, p_off, p_len, profile, is_ecc, le, depth, ch, srate, fsize, ratio, _, _, fflush, crc = row

@@ -263,8 +263,8 @@ def test_repair_short_tail_and_codesize_zero(bk):
 
 
 def test_plan_matches_the_reference_slicing():
-    from frad_python_amd.decoder import _strip_ecc
+    from frad_python_amd.frames import strip_ecc
     rng = np.random.default_rng(1)
     for dsize, cs in RATIOS + [(0, 5), (3, 250)]:
         for n in (0, 1, 2, cs, cs + 1, dsize + cs, 3 * (dsize + cs) + 1, 1000):
-            assert ecc.data_len(n, dsize, cs) == len(_strip_ecc(rng.bytes(n), dsize, cs))
+            assert ecc.data_len(n, dsize, cs) == len(strip_ecc(rng.bytes(n), dsize, cs))

@@ -482,3 +482,11 @@ def test_device_inflate_run_fallback_keeps_the_zero_frame():
             assert _zlib(bytes(s[p:p + 64])) is None
             ref = _same(bytes(s))
             assert ref.size
+
+
+@pytest.mark.gpu
+def test_device_inflate_run_costs_the_same_calls_whatever_its_length(monkeypatch):
+    """device_inflate=True: the fused run from the deflated payloads on makes the same C-ABI calls for 8 frames and for 64"""
+    from test_stream import decoder_call_counts
+    few, many = decoder_call_counts(monkeypatch, 1, 2048, 2, 16, 16, device_inflate=True)
+    assert few == many and few["inflate_raw"] == 1

@@ -344,3 +344,87 @@ def test_streaming_api_under_random_chunking():
         got = np.concatenate([x for x in pieces if x.size])
         assert got.shape == want.shape, (it, p, got.shape, want.shape)
         assert np.max(np.abs(got - want)) <= 1e-12 * max(1.0, np.max(np.abs(want))), (it, p)
+
+
+# ------------------------------------------------------------------------------------------- runs: how a stream is cut up
+class LoggingBridge:
+    """A bridge that notes (method, number of frames) of every decode call it passes on"""
+    DECODES = {"lossless_decode": 1, "p1_decode_bodies": 0, "overlap_add": 0}         # method -> index of its frames argument
+
+    def __init__(self, inner):
+        self.inner, self.log = inner, []
+
+    def __getattr__(self, name):
+        v = getattr(self.inner, name)
+        if name not in self.DECODES:
+            return v
+
+        def call(*a, **k):
+            self.log.append((name, len(a[self.DECODES[name]])))
+            return v(*a, **k)
+        return call
+
+
+@pytest.mark.parametrize("frames", [8, 64])
+@pytest.mark.parametrize("profile,N,C,bits,ratio", [(0, 128, 1, 16, 0), (4, 128, 2, 24, 0), (1, 128, 1, 16, 2), (1, 256, 2, 16, 16)])
+def test_both_parsers_cut_the_same_runs(profile, N, C, bits, ratio, frames):
+    """The byte-wise parser ("host") and the native scanner ("host-scan") hand the bridge the same runs, whole or in pieces:
+    a frame completed from a carried-over header joins the scanned frames behind it.  The PCM alone cannot tell -- a run
+    that splits decodes to the same samples with more launches."""
+    cut = N * (ratio - 1) // ratio if ratio else N
+    pcm = synth.to_pcm(synth.harmonic_mix((frames - 1) * cut + N + cut // 3, C, 48000, seed=frames + N), "s16le").tobytes()
+    p = dict(profile=profile, srate=48000, channels=C, bits=bits, frame_size=N, pcm_format="s16le", overlap_ratio=ratio)
+    stream, _ = _encode("host", pcm, 1 << 20, p)
+    for cuts in ((), (1, 333, len(stream) // 2, len(stream) - 5)):
+        got = {}
+        for kind in ("host", "host-scan"):
+            br = LoggingBridge(_bridge(kind))
+            dec = Decoder(bridge=br)
+            out, n, prev = [], 0, 0
+            for c in cuts + (len(stream),):
+                d = dec.process(stream[prev:c]); out.append(d.pcm.reshape(-1, C)); n += d.frames; prev = c
+            out.append(dec.flush().pcm.reshape(-1, C))
+            assert n == frames + 1, (kind, cuts, n)
+            got[kind] = (br.log, np.concatenate(out).tobytes())
+        print(f"[runs] p{profile} N={N} C={C} {frames} frames, cuts {cuts}: {got['host'][0]}")
+        assert got["host"][0] == got["host-scan"][0], (cuts, got["host"][0], got["host-scan"][0])
+        assert got["host"][1] == got["host-scan"][1], cuts
+        assert max(k for _, k in got["host"][0]) >= (frames if not cuts else frames // 4)         # really runs, not frame by frame
+
+
+def decoder_call_counts(monkeypatch, profile, N, C, bits, ratio, **decoder_kw) -> list:
+    """The C-ABI calls (name -> count, on the loaded library) of one process() + flush() over the first 8 and the first 64
+    frames of one encoder-written stream: one geometry, so one run each."""
+    from frad_python_amd import _lib
+    from frad_python_amd.bridge import HipBridge
+    from test_batch_decode import Counting
+    cut = N * (ratio - 1) // ratio if ratio else N
+    pcm = synth.to_pcm(synth.harmonic_mix(65 * cut + N, C, 48000, seed=N + profile), "s16le").tobytes()
+    enc = Encoder(profile, 48000, C, bits, N, "s16le", allow_profile2=True)
+    enc.set_overlap_ratio(ratio)
+    stream = enc.process(pcm).buf + enc.flush().buf
+    rows, _, _ = HipBridge().scan_lib.asfh_scan(stream, 0)
+    rows = rows.tolist()
+    assert len(rows) > 64 and len({r[3:13] for r in rows[:64]}) == 1       # one geometry
+    counts = []
+    for n in (8, 64):
+        c = {}
+        monkeypatch.setattr(_lib, "_lib", Counting(_lib.load(), c))          # every C-ABI call of the loaded library
+        dec = Decoder(bridge=HipBridge(), **decoder_kw)
+        d = dec.process(stream[:rows[n][0]])
+        tail = dec.flush()
+        monkeypatch.undo()
+        assert d.frames == n and d.pcm.size + tail.pcm.size == n * cut * C + (N - cut) * C
+        counts.append(c)
+        print(f"[calls] p{profile} N={N} C={C} {decoder_kw}, {n} frames: {dict(sorted(c.items()))}")
+    return counts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("profile,N,C,bits,ratio,out_format", [(0, 2048, 2, 32, 0, None), (0, 2048, 2, 32, 0, "s16le"),
+                                                               (1, 2048, 2, 16, 16, None), (1, 256, 1, 16, 2, None),
+                                                               (2, 256, 1, 16, 2, None)])
+def test_a_run_costs_the_same_calls_whatever_its_length(monkeypatch, profile, N, C, bits, ratio, out_format):
+    """One upload, one chain, one download per run: 8 frames and 64 make the same C-ABI calls."""
+    few, many = decoder_call_counts(monkeypatch, profile, N, C, bits, ratio, out_format=out_format)
+    assert few == many
