@@ -153,11 +153,9 @@ namespace {
 
 std::mutex g_mu;
 std::map<int, uint32_t*> g_tab;                              // device -> tables
-thread_local int g_last = 0;
-#define CCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last = (int)e_; return FRAD_E_HIP; } } while (0)
 
 int get_crc_tables(const uint32_t** out) {
-    int dev = 0; CCHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_tab.find(dev);
     if (it != g_tab.end()) { *out = it->second; return FRAD_OK; }
@@ -177,8 +175,8 @@ int get_crc_tables(const uint32_t** out) {
             m[k * 32 + j] = r;
         }
     uint32_t* d = nullptr;
-    CCHK(hipMalloc(&d, h.size() * sizeof(uint32_t)));
-    CCHK(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&d, h.size() * sizeof(uint32_t)));
+    FRAD_HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     g_tab[dev] = d; *out = d;
     return FRAD_OK;
 }
@@ -186,7 +184,7 @@ int get_crc_tables(const uint32_t** out) {
 std::map<int, uint32_t*> g_tab16;                            // device -> CRC-16 tables
 
 int get_crc16_tables(const uint32_t** out) {
-    int dev = 0; CCHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_tab16.find(dev);
     if (it != g_tab16.end()) { *out = it->second; return FRAD_OK; }
@@ -206,15 +204,14 @@ int get_crc16_tables(const uint32_t** out) {
             m[k * 16 + j] = r;
         }
     uint32_t* d = nullptr;
-    CCHK(hipMalloc(&d, h.size() * sizeof(uint32_t)));
-    CCHK(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&d, h.size() * sizeof(uint32_t)));
+    FRAD_HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     g_tab16[dev] = d; *out = d;
     return FRAD_OK;
 }
 
 }  // namespace
 
-int crc_last_hip_error() { return g_last; }
 void crc_clear() {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_tab) (void)hipFree(kv.second);
@@ -233,14 +230,14 @@ extern "C" int frad_crc32_frames(const void* data, int64_t stride, int64_t n_fra
     const uint32_t* tables = nullptr;
     const int rc = get_crc_tables(&tables);
     if (rc != FRAD_OK) return rc;
-    const int aligned = ((reinterpret_cast<uintptr_t>(data) | (uintptr_t)stride) & 15u) == 0 ? 1 : 0;
+    const int aligned = (aligned16(data) && (stride & 15) == 0) ? 1 : 0;
     const size_t lds = (size_t)CRC_TAB_WORDS * 4 + 4 * 64 * (size_t)CRC_PAD;
     long long blocks = (n_frames + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     allow_lds(k_crc32_frames<0>, lds);
     hipLaunchKernelGGL(k_crc32_frames<0>, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char*>(data), (long long)stride, (long long)n_frames, (long long)nbytes, tables, crc_out, aligned);
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -258,6 +255,6 @@ extern "C" int frad_crc16_ansi_frames(const void* data, const int64_t* offsets, 
     allow_lds(k_crc16_frames, lds);
     hipLaunchKernelGGL(k_crc16_frames, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char*>(data), offsets, (long long)n_frames, tables, crc_out);
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

@@ -489,10 +489,7 @@ __global__ void __launch_bounds__(64) k_deflate(const unsigned char* __restrict_
     out_bytes[f] = d.opos;
 }
 
-thread_local int g_def_hip = 0;
-
 }  // namespace
-int deflate_last_hip_error() { return g_def_hip; }
 }  // namespace frad
 
 using namespace frad;
@@ -508,7 +505,7 @@ extern "C" int frad_deflate_raw(const void* src, const int64_t* src_offsets, int
     if (n_frames < 0) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!src || !src_offsets || !dst || !dst_bytes || !status) return FRAD_E_INVALID;
-    if (dst_stride < 16 || (dst_stride & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) return FRAD_E_INVALID;
+    if (dst_stride < 16 || (dst_stride & 15) || !aligned16(dst)) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
     // the longest body whose bound fits the row (and that zlib deflates without sliding its window)
     long long maxb = dst_stride - 7 - 6 * (dst_stride / (DF_LITBUF - 1) + 1);
@@ -530,7 +527,6 @@ extern "C" int frad_deflate_raw(const void* src, const int64_t* src_offsets, int
                            reinterpret_cast<const long long*>(src_offsets), static_cast<unsigned char*>(dst), (long long)dst_stride,
                            (int)maxb, reinterpret_cast<long long*>(dst_bytes), status);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_def_hip = (int)e; return FRAD_E_HIP; }
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

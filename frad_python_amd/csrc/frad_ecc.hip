@@ -388,11 +388,9 @@ namespace {
 
 std::mutex g_mu;
 std::map<std::pair<int, int>, unsigned char*> g_tab;       // (device, codesize) -> table
-thread_local int g_last = 0;
-#define ECHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last = (int)e_; return FRAD_E_HIP; } } while (0)
 
 int get_rs_tables(int cs, const unsigned char** out) {
-    int dev = 0; ECHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_tab.find({dev, cs});
     if (it != g_tab.end()) { *out = it->second; return FRAD_OK; }
@@ -415,8 +413,8 @@ int get_rs_tables(int cs, const unsigned char** out) {
     uint16_t* lgg = reinterpret_cast<uint16_t*>(h.data() + RS_LGG);
     for (int j = 0; j < 256; ++j) lgg[j] = (j < cs && gpoly[j]) ? h[RS_LOG + gpoly[j]] : (uint16_t)RS_ZERO;
     unsigned char* d = nullptr;
-    ECHK(hipMalloc(&d, RS_TAB));
-    ECHK(hipMemcpy(d, h.data(), RS_TAB, hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&d, RS_TAB));
+    FRAD_HIPCHK(hipMemcpy(d, h.data(), RS_TAB, hipMemcpyHostToDevice));
     g_tab[{dev, cs}] = d; *out = d;
     return FRAD_OK;
 }
@@ -442,7 +440,7 @@ int rs_launch(const void* in, const int64_t* in_off, const int64_t* blk_off, con
     hipLaunchKernelGGL(k_rs_blocks<MODE>, dim3((unsigned)rs_grid((n_blocks + 63) / 64)), dim3(64), lds, static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char*>(in), in_off, blk_off, out_off, (long long)n_frames, (long long)n_blocks,
                        (int)dsize, (int)codesize, tables, static_cast<unsigned char*>(out), work, stage_in, stage_out, ws);
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -451,7 +449,7 @@ int rs_check_args(const void* in, const int64_t* in_off, const int64_t* blk_off,
     if (n_frames < 0 || n_blocks < 0 || n_blocks > 0x7ffffffell) return FRAD_E_INVALID;
     if (n_frames > 0 && (!in_off || !blk_off || !out_off)) return FRAD_E_INVALID;
     if (n_blocks > 0 && (!in || !out)) return FRAD_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return FRAD_E_INVALID;
+    if (!aligned16(in) || !aligned16(out)) return FRAD_E_INVALID;
     return FRAD_OK;
 }
 
@@ -467,7 +465,7 @@ int rsf_width(int cs) {
 }
 
 int get_rs_prod(int cs, const uint32_t** out) {
-    int dev = 0; ECHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_prod.find({dev, cs});
     if (it != g_prod.end()) { *out = it->second; return FRAD_OK; }
@@ -495,8 +493,8 @@ int get_rs_prod(int cs, const uint32_t** out) {
             h[(size_t)fb * WM + a / 4] |= mul(fb, gpoly[j]) << (8 * (a & 3));
         }
     uint32_t* d = nullptr;
-    ECHK(hipMalloc(&d, h.size() * 4));
-    ECHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&d, h.size() * 4));
+    FRAD_HIPCHK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     g_prod[{dev, cs}] = d; *out = d;
     return FRAD_OK;
 }
@@ -519,13 +517,12 @@ int rsf_launch(const unsigned char* in, long long in_stride, long long n_frames,
     allow_lds(k_rs_frames<WM>, lds);
     hipLaunchKernelGGL(k_rs_frames<WM>, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * RSF_WAVES), lds, s, in, in_stride,
                        n_frames, nbytes, dsize, cs, prod, out, out_stride, nblk, upf, dpitch, cpitch, aligned_in, aligned_out, wide);
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
 }  // namespace
 
-int ecc_last_hip_error() { return g_last; }
 void ecc_clear() {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_tab) (void)hipFree(kv.second);
@@ -555,11 +552,11 @@ extern "C" int frad_rs_repair(const void* in, const int64_t* in_off, const int64
     if (n_frames > 0 && (!corrected || !failed)) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(corrected, 0, (size_t)n_frames * 4, s) != hipSuccess || hipMemsetAsync(failed, 0, (size_t)n_frames * 4, s) != hipSuccess)
-        return FRAD_E_HIP;
+    FRAD_HIPCHK(hipMemsetAsync(corrected, 0, (size_t)n_frames * 4, s));
+    FRAD_HIPCHK(hipMemsetAsync(failed, 0, (size_t)n_frames * 4, s));
     if (n_blocks == 0) return FRAD_OK;
     if (!work) return FRAD_E_INVALID;
-    if (hipMemsetAsync(work, 0, 4, s) != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipMemsetAsync(work, 0, 4, s));
     rc = rs_launch<1>(in, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, work, stream);
     if (rc != FRAD_OK) return rc;
     const unsigned char* tables = nullptr;
@@ -569,7 +566,7 @@ extern "C" int frad_rs_repair(const void* in, const int64_t* in_off, const int64
     hipLaunchKernelGGL(k_rs_fix, dim3((unsigned)rs_grid(n_blocks)), dim3(64), lds, s, static_cast<const unsigned char*>(in), in_off,
                        blk_off, out_off, (long long)n_frames, (int)dsize, (int)codesize, tables, static_cast<unsigned char*>(out),
                        static_cast<const int32_t*>(work), corrected, failed);
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 

@@ -262,37 +262,6 @@ int launch_from_f64(int dtype, const unsigned char* in, unsigned char* out, long
     return FRAD_OK;
 }
 
-bool valid_out_dtype(int d) {
-    if (d < 0 || d > 23) return false;
-    const int kind = d >> 3, lg = (d >> 1) & 3, be = d & 1;
-    return !(kind == 2 && lg == 0) && !(lg == 0 && be);
-}
-
-// exp(-i pi p / q), the generator the wave table blob is built with (same values as frad_hip.hip's unit_neg)
-void epi_unit_neg(long long p, long long q, long double& re, long double& im) {
-    const long double PI = 3.14159265358979323846264338327950288419716939937510L;
-    long long r = p % (2 * q); if (r < 0) r += 2 * q;
-    const long long h = q / 2;
-    const int quad = (int)(r / h);
-    const long long rem = r % h;
-    long double c, sn;
-    if (4 * rem <= q) { c = cosl(PI * (long double)rem / (long double)q); sn = sinl(PI * (long double)rem / (long double)q); }
-    else { c = sinl(PI * (long double)(h - rem) / (long double)q); sn = cosl(PI * (long double)(h - rem) / (long double)q); }
-    if (rem == 0) { c = 1.0L; sn = 0.0L; }
-    long double C, S;
-    switch (quad) { case 0: C = c; S = sn; break; case 1: C = -sn; S = c; break; case 2: C = -c; S = -sn; break; default: C = sn; S = -c; }
-    re = C; im = -S;
-}
-
-thread_local int g_epi_hip = 0;
-#define EPICHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_epi_hip = (int)e_; return FRAD_E_HIP; } } while (0)
-
-struct Scratch {                                               // stream-ordered float64 staging for the two-pass decodes
-    hipStream_t s; void* p = nullptr;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() { if (p) (void)hipFreeAsync(p, s); }
-};
-
 }  // namespace
 }  // namespace frad
 
@@ -305,21 +274,21 @@ extern "C" long long frad_debug_second_passes(void) { return g_second_passes.loa
 extern "C" {
 
 int frad_from_f64(const double* pcm, int64_t n_values, int32_t out_dtype, uint32_t flags, void* out, void* stream) {
-    if (n_values < 0 || !valid_out_dtype(out_dtype)) return FRAD_E_INVALID;
+    if (n_values < 0 || !valid_pcm_dtype(out_dtype)) return FRAD_E_INVALID;
     if (n_values == 0) return FRAD_OK;
     if (!pcm || !out) return FRAD_E_INVALID;
     Geom g{}; g.N = 1; g.C = 1; g.bits = 64; g.raw_be = (flags & FRAD_RAW_BE_INTS) ? 1 : 0;
     const int rc = launch_from_f64<0>(out_dtype, reinterpret_cast<const unsigned char*>(pcm), static_cast<unsigned char*>(out), n_values, g,
                                       static_cast<hipStream_t>(stream));
     if (rc != FRAD_OK) return rc;
-    EPICHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
 int frad_p4_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
                         uint32_t flags, int32_t out_dtype, void* pcm_out, void* stream) {
-    if (n_frames < 0 || N < 1 || C < 1 || C > 256 || !valid_out_dtype(out_dtype)) return FRAD_E_INVALID;
-    if (!(bits == 12 || bits == 16 || bits == 24 || bits == 32 || bits == 48 || bits == 64)) return FRAD_E_INVALID;
+    if (n_frames < 0 || N < 1 || C < 1 || C > 256 || !valid_pcm_dtype(out_dtype)) return FRAD_E_INVALID;
+    if (!valid_bits(bits)) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!payload || !pcm_out || payload_stride < (int64_t)frad_payload_bytes(N, C, bits)) return FRAD_E_INVALID;
     Geom g{}; g.n_frames = n_frames; g.N = N; g.C = C; g.bits = bits; g.le = (flags & FRAD_LITTLE_ENDIAN) ? 1 : 0; g.payload_stride = payload_stride;
@@ -327,7 +296,7 @@ int frad_p4_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_f
     const int rc = launch_from_f64<1>(out_dtype, static_cast<const unsigned char*>(payload), static_cast<unsigned char*>(pcm_out),
                                       (long long)n_frames * N * C, g, static_cast<hipStream_t>(stream));
     if (rc != FRAD_OK) return rc;
-    EPICHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -335,7 +304,7 @@ int frad_p4_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_f
 // transform kernels write float64 and the narrowing pass follows on the same stream (stream-ordered scratch).
 int frad_p0_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
                         uint32_t flags, int32_t out_dtype, void* pcm_out, void* stream) {
-    if (!valid_out_dtype(out_dtype)) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(out_dtype)) return FRAD_E_INVALID;
     if (out_dtype == FRAD_PCM_F64LE) return frad_p0_digital(payload, payload_stride, n_frames, N, C, bits, flags, static_cast<double*>(pcm_out), stream);
     if (n_frames < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
@@ -345,11 +314,8 @@ int frad_p0_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_f
         Geom g{};
         g.n_frames = n_frames; g.frame_stride = N; g.payload_stride = payload_stride; g.N = N; g.C = C; g.bits = bits;
         g.le = (flags & FRAD_LITTLE_ENDIAN) ? 1 : 0; g.dtype = FRAD_PCM_F64LE; g.fpb = 1; g.n_valid = N; g.cg = C;
-        const int ai = ((reinterpret_cast<uintptr_t>(payload) & 15) == 0 && payload_stride % 16 == 0) ? 1 : 0;
-        if (launch_p0_inv_wave_pcm(s, static_cast<const unsigned char*>(payload), pcm_out, g, ai, out_dtype, epi_unit_neg)) {
-            EPICHK(hipGetLastError());
-            return FRAD_OK;
-        }
+        const int ai = (aligned16(payload) && payload_stride % 16 == 0) ? 1 : 0;
+        FRAD_TRY_LAUNCH(launch_p0_inv_wave_pcm(s, static_cast<const unsigned char*>(payload), pcm_out, g, ai, out_dtype));
     }
     {   // every other LDS-resident kernel converts in its own store (one pass, no scratch); only the unit / two-pass whole-row kernels'
         // geometries are rerouted to their one-shot twins for it, and frames wider than a CU keep the second pass
@@ -359,15 +325,16 @@ int frad_p0_digital_pcm(const void* payload, int64_t payload_stride, int64_t n_f
     g_second_passes.fetch_add(1, std::memory_order_relaxed);
     Scratch ws(s);
     const size_t n = (size_t)n_frames * N * C;
-    if (hipMallocAsync(&ws.p, n * 8, s) != hipSuccess) return FRAD_E_NOMEM;
-    int rc = frad_p0_digital(payload, payload_stride, n_frames, N, C, bits, flags, static_cast<double*>(ws.p), stream);
+    int rc = ws.alloc(n * 8);
+    if (rc != FRAD_OK) return rc;
+    rc = frad_p0_digital(payload, payload_stride, n_frames, N, C, bits, flags, static_cast<double*>(ws.p), stream);
     if (rc != FRAD_OK) return rc;
     return frad_from_f64(static_cast<const double*>(ws.p), (int64_t)n, out_dtype, flags, pcm_out, stream);
 }
 
 int frad_p1_digital_pcm(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_t N, int32_t C, int32_t bits, int32_t srate,
                         int32_t out_dtype, uint32_t flags, void* pcm_out, void* stream) {
-    if (!valid_out_dtype(out_dtype)) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(out_dtype)) return FRAD_E_INVALID;
     if (out_dtype == FRAD_PCM_F64LE) return frad_p1_digital(q, tq, n_frames, N, C, bits, srate, static_cast<double*>(pcm_out), stream);
     if (n_frames < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
@@ -379,15 +346,16 @@ int frad_p1_digital_pcm(const int32_t* q, const int32_t* tq, int64_t n_frames, i
     g_second_passes.fetch_add(1, std::memory_order_relaxed);
     Scratch ws(s);
     const size_t n = (size_t)n_frames * N * C;
-    if (hipMallocAsync(&ws.p, n * 8, s) != hipSuccess) return FRAD_E_NOMEM;
-    int rc = frad_p1_digital(q, tq, n_frames, N, C, bits, srate, static_cast<double*>(ws.p), stream);
+    int rc = ws.alloc(n * 8);
+    if (rc != FRAD_OK) return rc;
+    rc = frad_p1_digital(q, tq, n_frames, N, C, bits, srate, static_cast<double*>(ws.p), stream);
     if (rc != FRAD_OK) return rc;
     return frad_from_f64(static_cast<const double*>(ws.p), (int64_t)n, out_dtype, flags, pcm_out, stream);
 }
 
 int frad_p1_overlap_add_pcm(const double* frames, int64_t n_frames, int32_t N, int32_t C, int32_t overlap_ratio, const double* prev_tail,
                             int32_t out_dtype, uint32_t flags, void* ola_out, double* next_tail, void* stream) {
-    if (!valid_out_dtype(out_dtype)) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(out_dtype)) return FRAD_E_INVALID;
     if (out_dtype == FRAD_PCM_F64LE) return frad_p1_overlap_add(frames, n_frames, N, C, overlap_ratio, prev_tail, static_cast<double*>(ola_out), next_tail, stream);
     if (n_frames < 0 || N < 1 || C < 1 || overlap_ratio < 2 || overlap_ratio > 256) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
@@ -409,14 +377,14 @@ int frad_p1_overlap_add_pcm(const double* frames, int64_t n_frames, int32_t N, i
         default: return FRAD_E_INVALID;
     }
 #undef GO
-    EPICHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
 int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
                            const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
                            int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off, int64_t out_rows, void* stream) {
-    if (!valid_out_dtype(out_dtype) || n_clips < 0 || out_rows < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(out_dtype) || n_clips < 0 || out_rows < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
     if (overlap_ratio != 0 && (overlap_ratio < 2 || overlap_ratio > 256)) return FRAD_E_INVALID;
     if (n_clips == 0 || out_rows == 0) return FRAD_OK;
     if (!clip_frame0 || !tail_off || !tail_rows || !out_off || !out) return FRAD_E_INVALID;
@@ -439,7 +407,7 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
         default: return FRAD_E_INVALID;
     }
 #undef GO
-    EPICHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 

@@ -144,15 +144,6 @@ __global__ void __launch_bounds__(256) k_g_p1_dequant(const int32_t* __restrict_
     }
 }
 
-thread_local int g_glob_hip = 0;
-#define GCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_glob_hip = (int)e_; return FRAD_E_HIP; } } while (0)
-
-struct Ws {                                            // stream-ordered scratch, released on every path out
-    hipStream_t s; void* p = nullptr;
-    explicit Ws(hipStream_t st) : s(st) {}
-    int get(size_t bytes) { return hipMallocAsync(&p, bytes, s) == hipSuccess ? FRAD_OK : FRAD_E_NOMEM; }
-    ~Ws() { if (p) (void)hipFreeAsync(p, s); }
-};
 long long frames_per_chunk(long long n_frames, int N, int C) {
     const long long per = (long long)N * C * 8;
     long long k = (128LL << 20) / per;
@@ -168,7 +159,7 @@ template <bool FWD>
 int rows_dct(const double* in, double* out, void* zw, const double* ct, int N, int C, long long rows, long long fstride, long long cstride,
              long long ostride, hipStream_t s) {
     if (zw != nullptr) {
-        const int r = global_dct_mixed(FWD, in, out, zw, N, C, rows, fstride, cstride, ostride, s, unit_root);
+        const int r = global_dct_mixed(FWD, in, out, zw, N, C, rows, fstride, cstride, ostride, s);
         if (r != 0) return r < 0 ? r : FRAD_OK;
     }
     hipLaunchKernelGGL(k_g_dct<FWD>, dct_grid(N, rows), dim3(256), TN * 8, s, in, out, ct, N, C, fstride, cstride, ostride, dct_bpr(N));
@@ -183,8 +174,6 @@ bool mixed_length(int N) {                                   // N = 2 r 2^p, r i
 
 }  // namespace
 
-int global_last_hip_error() { return g_glob_hip; }
-
 // profile 0 encode of frames [0, n_frames) through the workspaces.  `g` as frad_p0_analogue builds it.
 int global_p0_analogue(const unsigned char* pcm, unsigned char* payload, double* absmax, const Geom& g, uint32_t flags, hipStream_t s) {
     const int N = g.N, C = g.C;
@@ -192,9 +181,9 @@ int global_p0_analogue(const unsigned char* pcm, unsigned char* payload, double*
     DirectTable d; int rc = get_direct(N, d);
     if (rc != FRAD_OK) return rc;
     const long long chunk = frames_per_chunk(g.n_frames, N, C);
-    Ws xw(s), Xw(s), zw(s);
-    if ((rc = xw.get((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
-    if (mixed_length(N) && (rc = zw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    Scratch xw(s), Xw(s), zw(s);
+    if ((rc = xw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    if (mixed_length(N) && (rc = zw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
     for (long long f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const long long nf = g.n_frames - f0 < chunk ? g.n_frames - f0 : chunk;
         Geom gs = g; gs.fpb = stage_bpf(N, C);
@@ -202,7 +191,7 @@ int global_p0_analogue(const unsigned char* pcm, unsigned char* payload, double*
         // coefficient rows interleaved [frame][k][c]: the order profile 0 packs them in (freqs.T.ravel(), profile0.py:29)
         rc = rows_dct<true>(static_cast<const double*>(xw.p), static_cast<double*>(Xw.p), zw.p, d.ct, N, C, nf * C, (long long)N * C, 1LL, (long long)C, s);
         if (rc != FRAD_OK) return rc;
-        GCHK(hipGetLastError());
+        FRAD_HIPCHK(hipGetLastError());
         rc = frad_p4_analogue(Xw.p, FRAD_PCM_F64LE, nf, N, C, N, g.bits, flags & FRAD_LITTLE_ENDIAN, payload + f0 * g.payload_stride,
                               g.payload_stride, absmax ? absmax + f0 : nullptr, s);
         if (rc != FRAD_OK) return rc;
@@ -216,9 +205,9 @@ int global_p0_digital(const unsigned char* payload, double* out, const Geom& g, 
     DirectTable d; int rc = get_direct(N, d);
     if (rc != FRAD_OK) return rc;
     const long long chunk = frames_per_chunk(g.n_frames, N, C);
-    Ws Xi(s), Xp(s), zw(s);
-    if ((rc = Xi.get((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xp.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
-    if (mixed_length(N) && (rc = zw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    Scratch Xi(s), Xp(s), zw(s);
+    if ((rc = Xi.alloc((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xp.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    if (mixed_length(N) && (rc = zw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
     for (long long f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const long long nf = g.n_frames - f0 < chunk ? g.n_frames - f0 : chunk;
         rc = frad_p4_digital(payload + f0 * g.payload_stride, g.payload_stride, nf, N, C, g.bits, flags & FRAD_LITTLE_ENDIAN,
@@ -231,7 +220,7 @@ int global_p0_digital(const unsigned char* payload, double* out, const Geom& g, 
                            static_cast<double*>(Xp.p), gi, 0LL);
         rc = rows_dct<false>(static_cast<const double*>(Xp.p), out + f0 * (long long)N * C, zw.p, d.ct, N, C, nf * C, (long long)N * C, 1LL, (long long)C, s);
         if (rc != FRAD_OK) return rc;
-        GCHK(hipGetLastError());
+        FRAD_HIPCHK(hipGetLastError());
     }
     return FRAD_OK;
 }
@@ -241,9 +230,9 @@ int global_p1_analogue(const unsigned char* pcm, int32_t* q, int32_t* tq, const 
     DirectTable d; int rc = get_direct(N, d);
     if (rc != FRAD_OK) return rc;
     const long long chunk = frames_per_chunk(g.n_frames, N, C);
-    Ws xw(s), Xw(s), zw(s);
-    if ((rc = xw.get((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
-    if (mixed_length(N) && (rc = zw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    Scratch xw(s), Xw(s), zw(s);
+    if ((rc = xw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK || (rc = Xw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    if (mixed_length(N) && (rc = zw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
     const size_t lds = p1_scratch_bytes(1, N);
     for (long long f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const long long nf = g.n_frames - f0 < chunk ? g.n_frames - f0 : chunk;
@@ -252,7 +241,7 @@ int global_p1_analogue(const unsigned char* pcm, int32_t* q, int32_t* tq, const 
         rc = rows_dct<true>(static_cast<const double*>(xw.p), static_cast<double*>(Xw.p), zw.p, d.ct, N, C, nf * C, (long long)N * C, (long long)N, 1LL, s);   // planar rows for the band sums
         if (rc != FRAD_OK) return rc;
         hipLaunchKernelGGL(k_g_p1_quant, dim3((unsigned)(nf * C)), dim3(256), lds, s, static_cast<const double*>(Xw.p), q, tq, g, tb, f0);
-        GCHK(hipGetLastError());
+        FRAD_HIPCHK(hipGetLastError());
     }
     return FRAD_OK;
 }
@@ -262,16 +251,16 @@ int global_p1_digital(const int32_t* q, const int32_t* tq, double* out, const Ge
     DirectTable d; int rc = get_direct(N, d);
     if (rc != FRAD_OK) return rc;
     const long long chunk = frames_per_chunk(g.n_frames, N, C);
-    Ws Xw(s), zw(s);
-    if ((rc = Xw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
-    if (mixed_length(N) && (rc = zw.get((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    Scratch Xw(s), zw(s);
+    if ((rc = Xw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
+    if (mixed_length(N) && (rc = zw.alloc((size_t)chunk * N * C * 8)) != FRAD_OK) return rc;
     const size_t lds = p1_scratch_bytes(1, N);
     for (long long f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const long long nf = g.n_frames - f0 < chunk ? g.n_frames - f0 : chunk;
         hipLaunchKernelGGL(k_g_p1_dequant, dim3((unsigned)(nf * C)), dim3(256), lds, s, q, tq, static_cast<double*>(Xw.p), g, tb, f0);
         rc = rows_dct<false>(static_cast<const double*>(Xw.p), out + f0 * (long long)N * C, zw.p, d.ct, N, C, nf * C, (long long)N * C, 1LL, (long long)C, s);
         if (rc != FRAD_OK) return rc;
-        GCHK(hipGetLastError());
+        FRAD_HIPCHK(hipGetLastError());
     }
     return FRAD_OK;
 }

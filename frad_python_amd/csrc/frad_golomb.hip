@@ -20,6 +20,7 @@
 //                  lane's stream through LDS per round.  Semantics of the reference decoder incl. its end conditions (a
 //                  run of zero bits ends the stream; a code cut short by the end of the buffer is read from the bits there).
 #include "frad_common.hpp"
+#include "frad_host.hpp"
 #include "../../include/frad_hip.h"
 #include <cstdlib>
 
@@ -771,44 +772,63 @@ __global__ void __launch_bounds__(64) k_p2_prefix(const unsigned char* __restric
     decode_stream_wave(b + 2, ok ? llen : 0, lpc + (live ? f * nlpc : 0), live ? nlpc : 0);
 }
 
-thread_local int g_gol_hip = 0;
-#define GOLCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_gol_hip = (int)e_; return FRAD_E_HIP; } } while (0)
-
 }  // namespace
-int golomb_last_hip_error() { return g_gol_hip; }
 }  // namespace frad
 
 using namespace frad;
 
 namespace {
+// LDS budget of the wave-per-frame decoder.  wmax: stream words held per wave, 16 bits per coefficient on average (a frame
+// above that goes to the slow kernel): at N C = 4096 that is 8.4 KiB of stream per wave.  omax: a short stream's values on
+// their way out (the thresholds; a frame of <= 512 coefficients).  Staging whole frames of 4096 was measured: 25 KiB per
+// wave leaves six waves on a CU -- 0.46 ms per 15 000 frames against 0.37 without
+struct WaveBudget { int wmax, omax; };
+WaveBudget gol_wave_budget(int N, int C) {
+    long long wmax = ((long long)N * C * 16) / 32 + 64;
+    if (wmax > GW_WORDS) wmax = GW_WORDS;
+    const long long nq = (long long)N * C, nst = nq <= 512 ? nq : 27LL * C;
+    return {(int)wmax, (int)(nst + (nst >> 5) + 1)};
+}
+// the wave-per-frame kernel, then (with_maps) its second launch for the streams the walks did not settle: the entry maps
+void gol_decode_wave(const void* bodies, const int64_t* offsets, const long long* starts, int64_t n_frames, int32_t N, int32_t C,
+                     int32_t* q, int32_t* tq, int32_t* status, int32_t* todo, bool with_maps, hipStream_t s) {
+    const WaveBudget b = gol_wave_budget(N, C);
+    hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds(b.wmax, b.omax), s, static_cast<const unsigned char*>(bodies),
+                       reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, b.wmax, b.omax, starts);
+    if (with_maps)                                            // (a wave whose frame has no unsettled stream returns at once)
+        hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds(b.wmax, b.omax, true), s, static_cast<const unsigned char*>(bodies),
+                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, b.wmax, b.omax, starts);
+}
 // the profile-1 streams of frame i start at starts[i] (NULL: offsets[i]) and end at offsets[i + 1]
 int gol_decode(const void* bodies, const int64_t* offsets, const long long* starts, int64_t n_frames, int32_t N, int32_t C,
                int32_t* q, int32_t* tq, int32_t* status, hipStream_t s) {
     const long long blocks = ((long long)n_frames + 63) / 64;
     static const bool no_wave = [] { const char* e = std::getenv("FRAD_TUNE_GOLOMB_LANE"); return e && e[0] == '1'; }();
-    int32_t* todo = nullptr;
+    Scratch todo(s);
     if (!no_wave) {
         // fast path: one wave per frame; what it cannot take (codes > 64 bits, k > 30, streams beyond its LDS) is marked in
         // `todo` and decoded by the lane-per-frame kernel behind it
-        if (hipMallocAsync(reinterpret_cast<void**>(&todo), sizeof(int32_t) * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
-        // LDS budget: 16 bits per coefficient on average (a frame above that goes to the slow kernel): at N C = 4096 that is
-        // 8.4 KiB of stream per wave
-        long long wmax = ((long long)N * C * 16) / 32 + 64;
-        if (wmax > GW_WORDS) wmax = GW_WORDS;
-        // + a short stream's values on their way out (the thresholds; a frame of <= 512 coefficients).  Staging whole frames of
-        // 4096 was measured: 25 KiB per wave leaves six waves on a CU -- 0.46 ms per 15 000 frames against 0.37 without
-        const long long nq = (long long)N * C, nst = nq <= 512 ? nq : 27LL * C;
-        const int omax = (int)(nst + (nst >> 5) + 1);
-        hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax), s, static_cast<const unsigned char*>(bodies),
-                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax, starts);
-        // behind it, for the streams the walks did not settle (a wave whose frame has none returns at once): the entry maps
-        hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax, true), s, static_cast<const unsigned char*>(bodies),
-                           reinterpret_cast<const long long*>(offsets), (long long)N * C, 27LL * C, q, tq, status, todo, (int)wmax, omax, starts);
+        const int rc = todo.alloc(sizeof(int32_t) * (size_t)n_frames);
+        if (rc != FRAD_OK) return rc;
+        gol_decode_wave(bodies, offsets, starts, n_frames, N, C, q, tq, status, todo.as<int32_t>(), true, s);
     }
     hipLaunchKernelGGL(k_gol_decode, dim3((unsigned)blocks), dim3(64), DEC_LDS, s, static_cast<const unsigned char*>(bodies),
-                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, (long long)N * C, 27LL * C, q, tq, status, todo, starts);
-    if (todo) (void)hipFreeAsync(todo, s);
-    GOLCHK(hipGetLastError());
+                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, (long long)N * C, 27LL * C, q, tq, status,
+                       todo.as<int32_t>(), starts);
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+// profile 1: '>I' thresholds length | thresholds | coefficients; profile 2 puts nlpc = 13 C LPC values in front (lpc != NULL)
+int gol_encode(const int32_t* q, const int32_t* tq, const int32_t* lpc, long long nlpc, int64_t n_frames, int32_t N, int32_t C,
+               void* bodies, int64_t body_stride, size_t bound, int64_t* body_bytes, void* stream) {
+    if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
+    if (n_frames == 0) return FRAD_OK;
+    if (!q || !tq || (nlpc && !lpc) || !bodies || !body_bytes) return FRAD_E_INVALID;
+    if (body_stride < (int64_t)bound || (body_stride & 3) || (reinterpret_cast<uintptr_t>(bodies) & 3)) return FRAD_E_INVALID;
+    if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_gol_encode, dim3((unsigned)n_frames), dim3(64), GOL_LDS, static_cast<hipStream_t>(stream), q, tq, (long long)N * C, 27LL * C,
+                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes), lpc, nlpc);
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 }  // namespace
@@ -824,16 +844,7 @@ size_t frad_p1_golomb_bound(int32_t N, int32_t C) {
 
 int frad_p1_golomb_encode(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_t N, int32_t C,
                           void* bodies, int64_t body_stride, int64_t* body_bytes, void* stream) {
-    if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
-    if (n_frames == 0) return FRAD_OK;
-    if (!q || !tq || !bodies || !body_bytes) return FRAD_E_INVALID;
-    if (body_stride < (int64_t)frad_p1_golomb_bound(N, C) || (body_stride & 3) || (reinterpret_cast<uintptr_t>(bodies) & 3)) return FRAD_E_INVALID;
-    if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_gol_encode, dim3((unsigned)n_frames), dim3(64), GOL_LDS, static_cast<hipStream_t>(stream), q, tq, (long long)N * C, 27LL * C,
-                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes),
-                       static_cast<const int32_t*>(nullptr), 0LL);
-    GOLCHK(hipGetLastError());
-    return FRAD_OK;
+    return gol_encode(q, tq, nullptr, 0, n_frames, N, C, bodies, body_stride, frad_p1_golomb_bound(N, C), body_bytes, stream);
 }
 
 size_t frad_p2_golomb_bound(int32_t N, int32_t C) {
@@ -844,15 +855,7 @@ size_t frad_p2_golomb_bound(int32_t N, int32_t C) {
 
 int frad_p2_golomb_encode(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C,
                           void* bodies, int64_t body_stride, int64_t* body_bytes, void* stream) {
-    if (n_frames < 0 || N < 1 || C < 1 || C > 256) return FRAD_E_INVALID;
-    if (n_frames == 0) return FRAD_OK;
-    if (!q || !tq || !lpc || !bodies || !body_bytes) return FRAD_E_INVALID;
-    if (body_stride < (int64_t)frad_p2_golomb_bound(N, C) || (body_stride & 3) || (reinterpret_cast<uintptr_t>(bodies) & 3)) return FRAD_E_INVALID;
-    if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_gol_encode, dim3((unsigned)n_frames), dim3(64), GOL_LDS, static_cast<hipStream_t>(stream), q, tq, (long long)N * C, 27LL * C,
-                       static_cast<unsigned char*>(bodies), (long long)body_stride, reinterpret_cast<long long*>(body_bytes), lpc, 13LL * C);
-    GOLCHK(hipGetLastError());
-    return FRAD_OK;
+    return gol_encode(q, tq, lpc, 13LL * C, n_frames, N, C, bodies, body_stride, frad_p2_golomb_bound(N, C), body_bytes, stream);
 }
 
 int frad_rows_compact(const void* rows, int64_t row_stride, const int64_t* row_bytes, int64_t n_rows, void* out, int64_t* offsets, void* stream) {
@@ -865,7 +868,7 @@ int frad_rows_compact(const void* rows, int64_t row_stride, const int64_t* row_b
     if (n_rows > 0 && out)
         hipLaunchKernelGGL(k_rows_gather, dim3((unsigned)n_rows), dim3(GT), 0, s, static_cast<const unsigned char*>(rows), (long long)row_stride,
                            reinterpret_cast<const long long*>(offsets), static_cast<unsigned char*>(out));
-    GOLCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -874,18 +877,8 @@ int frad_rows_compact(const void* rows, int64_t row_stride, const int64_t* row_b
 int frad_debug_golomb_decode_wave(const void* bodies, const int64_t* offsets, int64_t n_frames, int32_t N, int32_t C,
                                   int32_t* q, int32_t* tq, int32_t* todo, int32_t with_maps, void* stream) {
     if (n_frames <= 0 || N < 1 || C < 1 || !bodies || !offsets || !q || !tq || !todo || n_frames > 0x7fffffffLL) return FRAD_E_INVALID;
-    long long wmax = ((long long)N * C * 16) / 32 + 64;
-    if (wmax > GW_WORDS) wmax = GW_WORDS;
-    const long long nq = (long long)N * C, nst = nq <= 512 ? nq : 27LL * C;
-    const int omax = (int)(nst + (nst >> 5) + 1);
-    hipLaunchKernelGGL(k_gol_decode_wave<false>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax), static_cast<hipStream_t>(stream),
-                       static_cast<const unsigned char*>(bodies), reinterpret_cast<const long long*>(offsets), nq, 27LL * C, q, tq,
-                       static_cast<int32_t*>(nullptr), todo, (int)wmax, omax, static_cast<const long long*>(nullptr));
-    if (with_maps)
-        hipLaunchKernelGGL(k_gol_decode_wave<true>, dim3((unsigned)n_frames), dim3(64), gw_lds((int)wmax, omax, true), static_cast<hipStream_t>(stream),
-                           static_cast<const unsigned char*>(bodies), reinterpret_cast<const long long*>(offsets), nq, 27LL * C, q, tq,
-                           static_cast<int32_t*>(nullptr), todo, (int)wmax, omax, static_cast<const long long*>(nullptr));
-    GOLCHK(hipGetLastError());
+    gol_decode_wave(bodies, offsets, nullptr, n_frames, N, C, q, tq, nullptr, todo, with_maps != 0, static_cast<hipStream_t>(stream));
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -905,13 +898,12 @@ int frad_p2_golomb_decode(const void* bodies, const int64_t* offsets, int64_t n_
     if (!bodies || !offsets || !q || !tq || !lpc) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    long long* starts = nullptr;
-    if (hipMallocAsync(reinterpret_cast<void**>(&starts), sizeof(long long) * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+    Scratch starts(s);
+    const int rc = starts.alloc(sizeof(long long) * (size_t)n_frames);
+    if (rc != FRAD_OK) return rc;
     hipLaunchKernelGGL(k_p2_prefix, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), DEC_LDS, s, static_cast<const unsigned char*>(bodies),
-                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, 13LL * C, lpc, starts);
-    const int rc = gol_decode(bodies, offsets, starts, n_frames, N, C, q, tq, status, s);
-    (void)hipFreeAsync(starts, s);
-    return rc;
+                       reinterpret_cast<const long long*>(offsets), (long long)n_frames, 13LL * C, lpc, starts.as<long long>());
+    return gol_decode(bodies, offsets, starts.as<long long>(), n_frames, N, C, q, tq, status, s);
 }
 
 }  // extern "C"

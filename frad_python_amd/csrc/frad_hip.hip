@@ -14,27 +14,12 @@
 
 using namespace frad;
 
-namespace {
+namespace frad {
+int& last_hip_slot() { thread_local int slot = 0; return slot; }
 
-thread_local int g_last_hip = 0;
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last_hip = (int)e_; return FRAD_E_HIP; } } while (0)
-
-constexpr int kLdsBytes = 160 * 1024;     // CDNA4: 160 KiB LDS per CU, one workgroup may own it all
-
-bool valid_bits(int b) { return b == 12 || b == 16 || b == 24 || b == 32 || b == 48 || b == 64; }
-bool valid_dtype(int d) {
-    if (d < 0 || d > 23) return false;
-    const int kind = d >> 3, lg = (d >> 1) & 3, be = d & 1;
-    if (kind == 2 && lg == 0) return false;
-    if (lg == 0 && be) return false;
-    return true;
-}
-int log2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
-int gcd(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// exp(-i * pi * p / q) for even q, exact at the multiples of pi/2 and symmetric inside octants.
-void unit_neg(long long p, long long q, long double& re, long double& im) {
+// exp(-i * pi * p / q) for even q, exact at the multiples of pi/2 and symmetric inside octants: the one generator of every
+// twiddle table and LDS blob of the library (long double, rounded once to the table's type)
+void unit_root(long long p, long long q, long double& re, long double& im) {
     const long double PI = 3.14159265358979323846264338327950288419716939937510L;
     long long r = p % (2 * q); if (r < 0) r += 2 * q;
     const long long h = q / 2;                 // q is even
@@ -48,7 +33,13 @@ void unit_neg(long long p, long long q, long double& re, long double& im) {
     switch (quad) { case 0: C = c; S = s; break; case 1: C = -s; S = c; break; case 2: C = -c; S = -s; break; default: C = s; S = -c; }
     re = C; im = -S;
 }
+}  // namespace frad
+namespace {
 
+constexpr int kLdsBytes = 160 * 1024;     // CDNA4: 160 KiB LDS per CU, one workgroup may own it all
+
+int log2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
+int gcd(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
 std::mutex g_mu;
 std::map<std::tuple<int, int, int>, Tables> g_tables;        // (device, log2M, f32)
@@ -59,35 +50,34 @@ int build_tables(int log2m, Tables& out) {
     const int M = 1 << log2m, N = 2 * M;
     std::vector<cx<T>> tw(M), post(2 * (M / 2 + 1));
     for (int k = 0; k < M; ++k) {
-        long double re, im; unit_neg(2LL * k, M, re, im);
+        long double re, im; unit_root(2LL * k, M, re, im);
         tw[k].x = (T)re; tw[k].y = (T)im;
     }
     for (int k = 0; k <= M / 2; ++k) {
         long double re, im;
-        unit_neg(k, 2LL * N, re, im);              // w_k = exp(-i pi k / 2N)
+        unit_root(k, 2LL * N, re, im);              // w_k = exp(-i pi k / 2N)
         post[2 * k].x = (T)re; post[2 * k].y = (T)im;
-        unit_neg((long long)N + 5LL * k, 2LL * N, re, im);   // g_k = exp(-i pi (1/2 + 5k/2N))
+        unit_root((long long)N + 5LL * k, 2LL * N, re, im);   // g_k = exp(-i pi (1/2 + 5k/2N))
         post[2 * k + 1].x = (T)re; post[2 * k + 1].y = (T)im;
     }
-    HIPCHK(hipMalloc(&out.tw, tw.size() * sizeof(cx<T>)));
-    HIPCHK(hipMalloc(&out.post, post.size() * sizeof(cx<T>)));
-    HIPCHK(hipMemcpy(out.tw, tw.data(), tw.size() * sizeof(cx<T>), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(out.post, post.data(), post.size() * sizeof(cx<T>), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&out.tw, tw.size() * sizeof(cx<T>)));
+    FRAD_HIPCHK(hipMalloc(&out.post, post.size() * sizeof(cx<T>)));
+    FRAD_HIPCHK(hipMemcpy(out.tw, tw.data(), tw.size() * sizeof(cx<T>), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMemcpy(out.post, post.data(), post.size() * sizeof(cx<T>), hipMemcpyHostToDevice));
     std::vector<unsigned char> blob;
     for (int which = 0; which < 3; ++which) {                 // plan A, plan B, inverse plan I
-        if (!pers_blob_build(log2m, sizeof(T) == 4, which, blob, unit_neg)) continue;
+        if (!pers_blob_build(log2m, sizeof(T) == 4, which, blob)) continue;
         void*& dst = which == 0 ? out.blob : which == 1 ? out.blob_b : out.blob_i;
-        HIPCHK(hipMalloc(&dst, blob.size()));
-        HIPCHK(hipMemcpy(dst, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        FRAD_HIPCHK(hipMalloc(&dst, blob.size()));
+        FRAD_HIPCHK(hipMemcpy(dst, blob.data(), blob.size(), hipMemcpyHostToDevice));
     }
     return FRAD_OK;
 }
 
 }  // namespace
 namespace frad {
-void unit_root(long long p, long long q, long double& re, long double& im) { unit_neg(p, q, re, im); }
 int get_tables(int log2m, bool f32, Tables& out) {
-    int dev = 0; HIPCHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_tuple(dev, log2m, (int)f32);
     auto it = g_tables.find(key);
@@ -100,7 +90,7 @@ int get_tables(int log2m, bool f32, Tables& out) {
 }
 
 int get_direct(int N, DirectTable& out) {
-    int dev = 0; HIPCHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_pair(dev, N);
     auto it = g_direct.find(key);
@@ -110,10 +100,10 @@ int get_direct(int N, DirectTable& out) {
         g_direct.clear();
     }
     std::vector<double> ct(4 * (size_t)N);
-    for (long long j = 0; j < 4LL * N; ++j) { long double re, im; unit_neg(j, 2LL * N, re, im); ct[j] = (double)re; }
+    for (long long j = 0; j < 4LL * N; ++j) { long double re, im; unit_root(j, 2LL * N, re, im); ct[j] = (double)re; }
     DirectTable t;
-    HIPCHK(hipMalloc(&t.ct, ct.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(t.ct, ct.data(), ct.size() * sizeof(double), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(&t.ct, ct.size() * sizeof(double)));
+    FRAD_HIPCHK(hipMemcpy(t.ct, ct.data(), ct.size() * sizeof(double), hipMemcpyHostToDevice));
     g_direct[key] = t; out = t;
     return FRAD_OK;
 }
@@ -229,7 +219,7 @@ bool input_aligned(const void* pcm, long long frame_stride, int N, int C, int lg
 extern "C" {
 
 int frad_abi_version(void) { return FRAD_ABI_VERSION; }
-int frad_last_hip_error(void) { return g_last_hip; }
+int frad_last_hip_error(void) { return last_hip_slot(); }
 
 const char* frad_strerror(int status) {
     switch (status) {
@@ -253,7 +243,7 @@ int frad_plan_prepare(int32_t N, int32_t compute_f32) {
     const int l2 = log2_exact(N);
     if (l2 >= 7 && l2 <= 14) { Tables t; return get_tables(l2 - 1, compute_f32 != 0, t); }
     if (N < 1) return FRAD_E_INVALID;
-    { const int rc = mixed_prepare(N, unit_neg); if (rc != FRAD_OK) return rc; }
+    { const int rc = mixed_prepare(N); if (rc != FRAD_OK) return rc; }
     if (!compute_f32) { const int rc = blue_prepare(N); if (rc != FRAD_OK) return rc; }
     DirectTable d; return get_direct(N, d);
 }
@@ -275,11 +265,12 @@ int frad_p4_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
                      int32_t bits, uint32_t flags, void* payload, int64_t payload_stride, double* absmax, void* stream) {
     int rc = check_common(pcm, payload, n_frames, N, C, bits);
     if (rc != FRAD_OK) return rc;
-    if (!valid_dtype(pcm_dtype)) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(pcm_dtype)) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (payload_stride < (int64_t)frad_payload_bytes(N, C, bits)) return FRAD_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (absmax) HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)n_frames, s));
+    rc = zero_absmax(absmax, n_frames, s);                    // k_p4_pack accumulates with atomicMax
+    if (rc != FRAD_OK) return rc;
     const int lg = (pcm_dtype >> 1) & 3;
     Geom g = make_geom(n_frames, N, C, frame_stride, payload_stride, bits, flags, pcm_dtype);
     const long long NC = (long long)N * C;
@@ -305,7 +296,7 @@ int frad_p4_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     } else {
         hipLaunchKernelGGL(k_p4_pack_slow<0>, grid, dim3(256), 0, s, in, out, absmax, g, bpf);
     }
-    HIPCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -350,7 +341,7 @@ int frad_p4_digital(const void* payload, int64_t payload_stride, int64_t n_frame
     } else {
         hipLaunchKernelGGL(k_p4_unpack_slow<0>, grid, dim3(256), 0, s, in, pcm_out, g, bpf);
     }
-    HIPCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -366,7 +357,7 @@ int frad_p0_overflow_scan(const double* absmax, int64_t n_frames, int32_t bits, 
     long long blocks = (n_frames + 1023) / 1024;
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(k_overflow_scan<0>, dim3((unsigned)blocks), dim3(1024), 0, static_cast<hipStream_t>(stream), absmax, (long long)n_frames, lim, flag);
-    HIPCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -393,8 +384,66 @@ int frad_p0_analogue_clips(const void* pcm, int32_t pcm_dtype, int64_t n_clips, 
 }  // extern "C"
 namespace {
 
-// frames of the clips gathered into / scattered from a dense stream-ordered scratch (the kernels without clip addressing)
-struct StreamScratch { hipStream_t s; void* p = nullptr; ~StreamScratch() { if (p) (void)hipFreeAsync(p, s); } };
+// Profile 0 encode through every kernel but the wave one, offered in the fixed order half32, persistent, grp2, one-shot for
+// the LDS-resident power-of-two lengths and mixed-radix, Bluestein, workspace, direct for the others.  `g` may address
+// clips (g.fpc > 0): only the mixed-radix and Bluestein kernels follow that.  FRAD_OK = launched; 1 = clips, and the kernels
+// left have no clip addressing (the caller gathers them first); < 0 = FRAD_E_*.
+int p0_fwd_flat(const unsigned char* in, unsigned char* out, double* absmax, Geom g, int lg, bool f32, int ai, int ao,
+                uint32_t flags, hipStream_t s) {
+    const long long n_frames = g.n_frames;
+    const int N = g.N, C = g.C, bits = g.bits;
+    const FastCfg c = fast_cfg(N, C, f32);
+    if (g.fpc > 0 && (f32 || c.ok)) return 1;
+    int rc;
+    if (c.ok) {
+        Tables tb; rc = get_tables(c.log2m, f32, tb);
+        if (rc != FRAD_OK) return rc;
+        if (c.cg < C && bits == 12 && ((C & 1) || (c.cg & 1))) return global_p0_analogue(in, out, absmax, g, flags, s);   // pairs of values would straddle channel groups
+        g.fpb = c.fpb; g.cg = c.cg;
+        if (c.cg == C && ai) {                               // quad stage-in needs whole 16-byte rows / row groups
+            const int rb = C << lg;
+            g.in_mode = (rb <= 4 && 16 % rb == 0) ? 1 : rb == 8 ? 2 : rb % 16 == 0 ? 3 : 0;
+        }
+        if (c.cg == C && ao && C <= 2 && ((long long)N * C) % 32 == 0) g.cc_fast = C;
+        dim3 grid((unsigned)((n_frames + c.fpb - 1) / c.fpb));
+        if (f32 && c.log2m == 11 && C == 8 && c.cg == C) {      // BASELINE config 4's geometry: two half-frame blocks per frame
+            rc = zero_absmax(absmax, n_frames, s);
+            if (rc != FRAD_OK) return rc;
+            FRAD_TRY_LAUNCH(launch_p0_fwd_half32(lg, c, s, in, out, absmax, tb, g, ai, ao));
+        }
+        FRAD_TRY_LAUNCH(launch_p0_fwd_pers(f32, lg, c, s, in, out, absmax, tb, g, ao));
+        rc = zero_absmax(absmax, n_frames, s);
+        if (rc != FRAD_OK) return rc;
+        if (!f32 && c.cg < C) FRAD_TRY_LAUNCH(launch_p0_fwd_grp2(lg, c, s, in, out, absmax, tb, g, ai, ao));   // two channel groups with whole-row I/O
+        FRAD_TRY_LAUNCH(f32 ? launch_p0_fwd_f32(lg, c, grid, s, in, out, absmax, tb, g, ai, ao)
+                            : launch_p0_fwd_f64(lg, c, grid, s, in, out, absmax, tb, g, ai, ao));
+        return FRAD_E_UNSUPPORTED;
+    }
+    // N = 2 r 2^p, r in {3, 5, 7}: mixed-radix FFT (frad_mixed.hip), float64 for every PCM type
+    FRAD_TRY_LAUNCH(launch_p0_fwd_mixed(lg, s, in, out, absmax, g, ai, ao));
+    // any N in O(N log N): Bluestein over the power-of-two FFT
+    if (!f32) FRAD_TRY_LAUNCH(launch_p0_fwd_blue(lg, s, in, out, absmax, g, ao));
+    if (g.fpc > 0) return 1;
+    const size_t per_frame = 2 * (size_t)N * C * (f32 ? 4 : 8);
+    if (per_frame > (size_t)kLdsBytes) return global_p0_analogue(in, out, absmax, g, flags, s);   // wider than a CU's LDS: HBM workspaces (frad_global.hip)
+    DirectTable d; rc = get_direct(N, d);
+    if (rc != FRAD_OK) return rc;
+    rc = zero_absmax(absmax, n_frames, s);
+    if (rc != FRAD_OK) return rc;
+    g.fpb = direct_fpb(n_frames, C, per_frame);
+    const size_t lds = per_frame * (size_t)g.fpb;
+    const long long nblk = (n_frames + g.fpb - 1) / g.fpb;
+    if (nblk > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
+    dim3 grid((unsigned)nblk);
+    const dim3 blk((unsigned)direct_threads(N));
+#define FRAD_DIR(TT, LGV) do { allow_lds(k_p0_fwd_direct<TT, LGV>, lds); \
+        hipLaunchKernelGGL((k_p0_fwd_direct<TT, LGV>), grid, blk, lds, s, in, out, absmax, d.ct, g, ai, ao); } while (0)
+    if (f32) { if (lg == 1) FRAD_DIR(float, 1); else FRAD_DIR(float, 2); }
+    else switch (lg) { case 0: FRAD_DIR(double, 0); break; case 1: FRAD_DIR(double, 1); break; case 2: FRAD_DIR(double, 2); break; default: FRAD_DIR(double, 3); break; }
+#undef FRAD_DIR
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
 
 int p0_analogue_impl(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32_t N, int32_t C, int64_t frame_stride,
                      int32_t bits, uint32_t flags, void* payload, int64_t payload_stride, double* absmax,
@@ -402,7 +451,7 @@ int p0_analogue_impl(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     int rc = check_common(pcm, payload, n_frames, N, C, bits);
     if (rc == FRAD_OK && overflow_flag != nullptr && absmax == nullptr && n_frames > 0) return FRAD_E_INVALID;      // the test reads the per-frame maxima
     if (rc != FRAD_OK) return rc;
-    if (!valid_dtype(pcm_dtype)) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(pcm_dtype)) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (payload_stride < (int64_t)frad_payload_bytes(N, C, bits)) return FRAD_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -417,100 +466,105 @@ int p0_analogue_impl(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     {
         Geom gw = g;                                          // the wave kernels apply the overflow test themselves
         gw.ovf_flag = overflow_flag; gw.ovf_limit = storage_float_max(bits);
-        if (launch_p0_fwd_wave(lg, s, in, out, absmax, gw, ai, ao, unit_neg)) { HIPCHK(hipGetLastError()); return FRAD_OK; }
+        FRAD_TRY_LAUNCH(launch_p0_fwd_wave(lg, s, in, out, absmax, gw, ai, ao));
     }
-    if (fpc > 0 && (f32 || fast_cfg(N, C, f32).ok)) {
+    rc = p0_fwd_flat(in, out, absmax, g, lg, f32, ai, ao, flags, s);
+    if (rc == 1) {
         // clips through a kernel without clip addressing: the clips' frame regions are gathered into a dense scratch first
         // (one strided device copy), then the flat batch runs on it
         const size_t row = ((size_t)fpc * N * C) << lg;
-        StreamScratch ws{s};
-        if (hipMallocAsync(&ws.p, row * (size_t)(n_frames / fpc), s) != hipSuccess) return FRAD_E_NOMEM;
-        HIPCHK(hipMemcpy2DAsync(ws.p, row, pcm, ((size_t)clip_stride * C) << lg, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
+        Scratch ws(s);
+        rc = ws.alloc(row * (size_t)(n_frames / fpc));
+        if (rc != FRAD_OK) return rc;
+        FRAD_HIPCHK(hipMemcpy2DAsync(ws.p, row, pcm, ((size_t)clip_stride * C) << lg, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
         return p0_analogue_impl(ws.p, pcm_dtype, n_frames, N, C, frame_stride, bits, flags, payload, payload_stride, absmax, overflow_flag, stream, 0, 0);
     }
-    // every other kernel: the batch form of the test as a second launch on the same stream
-    const int rc_all = [&]() -> int {
-    const FastCfg c = fast_cfg(N, C, f32);
-    if (c.ok) {
-        Tables tb; rc = get_tables(c.log2m, f32, tb);
-        if (rc != FRAD_OK) return rc;
-        if (c.cg < C && bits == 12 && ((C & 1) || (c.cg & 1))) {       // pairs of values would straddle channel groups
-            const int r = global_p0_analogue(in, out, absmax, g, flags, s);
-            if (r == FRAD_E_HIP) g_last_hip = global_last_hip_error();
-            return r;
-        }
-        g.fpb = c.fpb; g.cg = c.cg;
-        if (c.cg == C && ai) {                               // quad stage-in needs whole 16-byte rows / row groups
-            const int rb = C << lg;
-            g.in_mode = (rb <= 4 && 16 % rb == 0) ? 1 : rb == 8 ? 2 : rb % 16 == 0 ? 3 : 0;
-        }
-        if (c.cg == C && ao && C <= 2 && ((long long)N * C) % 32 == 0) g.cc_fast = C;
-        dim3 grid((unsigned)((n_frames + c.fpb - 1) / c.fpb));
-        bool taken = false;
-        if (f32 && c.log2m == 11 && C == 8 && c.cg == C) {      // BASELINE config 4's geometry: two half-frame blocks per frame
-            if (absmax) HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)n_frames, s));   // atomicMax target
-            taken = launch_p0_fwd_half32(lg, c, s, in, out, absmax, tb, g, ai, ao) != 0;
-        }
-        if (taken) {
-        } else if (!launch_p0_fwd_pers(f32, lg, c, s, in, out, absmax, tb, g, ao)) {
-            if (absmax) HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)n_frames, s));   // atomicMax target
-            if (!f32 && c.cg < C && launch_p0_fwd_grp2(lg, c, s, in, out, absmax, tb, g, ai, ao)) {
-                // two channel groups with whole-row I/O took it (frad_p0_fwd_grp2.hip)
-            } else {
-                rc = f32 ? launch_p0_fwd_f32(lg, c, grid, s, in, out, absmax, tb, g, ai, ao)
-                         : launch_p0_fwd_f64(lg, c, grid, s, in, out, absmax, tb, g, ai, ao);
-                if (rc != FRAD_OK) return rc;
-            }
-        }
-    } else {
-        {                                                    // N = 2 r 2^p, r in {3, 5, 7}: mixed-radix FFT (frad_mixed.hip), float64 for every PCM type
-            const int r = launch_p0_fwd_mixed(lg, s, in, out, absmax, g, ai, ao, unit_neg);
-            if (r < 0) { if (r == FRAD_E_HIP) g_last_hip = mixed_last_hip_error(); return r; }
-            if (r == 1) return FRAD_OK;
-        }
-        if (!f32) {                                          // any N in O(N log N): Bluestein over the power-of-two FFT
-            const int r = launch_p0_fwd_blue(lg, s, in, out, absmax, g, ao);
-            if (r < 0) { if (r == FRAD_E_HIP) g_last_hip = blue_last_hip_error(); return r; }
-            if (r == 1) { HIPCHK(hipGetLastError()); return FRAD_OK; }
-        }
-        if (fpc > 0) {                                       // (Bluestein did not take it) gather the clips, then the flat batch
-            const size_t row = ((size_t)fpc * N * C) << lg;
-            StreamScratch ws{s};
-            if (hipMallocAsync(&ws.p, row * (size_t)(n_frames / fpc), s) != hipSuccess) return FRAD_E_NOMEM;
-            HIPCHK(hipMemcpy2DAsync(ws.p, row, pcm, ((size_t)clip_stride * C) << lg, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
-            return p0_analogue_impl(ws.p, pcm_dtype, n_frames, N, C, frame_stride, bits, flags, payload, payload_stride, absmax, nullptr, stream, 0, 0);
-        }
-        const size_t per_frame = 2 * (size_t)N * C * (f32 ? 4 : 8);
-        if (per_frame > (size_t)kLdsBytes) {                 // wider than a CU's LDS: HBM workspaces (frad_global.hip)
-            const int r = global_p0_analogue(in, out, absmax, g, flags, s);
-            if (r == FRAD_E_HIP) g_last_hip = global_last_hip_error();
-            return r;
-        }
-        DirectTable d; rc = get_direct(N, d);
-        if (rc != FRAD_OK) return rc;
-        if (absmax) HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)n_frames, s));
-        g.fpb = direct_fpb(n_frames, C, per_frame);
-        const size_t lds = per_frame * (size_t)g.fpb;
-        const long long nblk = (n_frames + g.fpb - 1) / g.fpb;
-        if (nblk > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
-        dim3 grid((unsigned)nblk);
-        const dim3 blk((unsigned)direct_threads(N));
-#define FRAD_DIR(TT, LGV) do { allow_lds(k_p0_fwd_direct<TT, LGV>, lds); \
-        hipLaunchKernelGGL((k_p0_fwd_direct<TT, LGV>), grid, blk, lds, s, in, out, absmax, d.ct, g, ai, ao); } while (0)
-        if (f32) { if (lg == 1) FRAD_DIR(float, 1); else FRAD_DIR(float, 2); }
-        else switch (lg) { case 0: FRAD_DIR(double, 0); break; case 1: FRAD_DIR(double, 1); break; case 2: FRAD_DIR(double, 2); break; default: FRAD_DIR(double, 3); break; }
-#undef FRAD_DIR
-    }
-    HIPCHK(hipGetLastError());
-    return FRAD_OK;
-    }();
-    if (rc_all != FRAD_OK) return rc_all;
+    if (rc != FRAD_OK) return rc;
+    // every kernel but the wave one: the batch form of the overflow test, once behind the transform on the same stream
     if (overflow_flag != nullptr) return frad_p0_overflow_scan(absmax, n_frames, bits, overflow_flag, stream);
     return FRAD_OK;
 }
 
+// Profile 0 decode through every kernel but the wave one: grp2, persistent, one-shot | mixed-radix, Bluestein, workspace,
+// direct.  `conv`: the store converts to g.dtype.  FRAD_OK = launched; 1 = not in one pass -- clips (g.fpc > 0) left to a
+// kernel without clip addressing, or a conversion that this geometry's kernel does not have; < 0 = FRAD_E_*.
+int p0_inv_flat(const unsigned char* in, double* pcm_out, Geom g, int ai, bool conv, uint32_t flags, hipStream_t s) {
+    const long long n_frames = g.n_frames;
+    const int N = g.N, C = g.C;
+    const FastCfg c = fast_cfg(N, C, false);
+    int rc;
+    if (c.ok) {
+        if (g.fpc > 0) return 1;
+        Tables tb; rc = get_tables(c.log2m, false, tb);
+        if (rc != FRAD_OK) return rc;
+        // (12-bit pairs may straddle channel groups here: unpacking only reads them; the packing side refuses that)
+        g.fpb = c.fpb; g.cg = c.cg;
+        if (c.cg == C && ai && C <= 2 && ((long long)N * C) % 32 == 0) g.cc_fast = C;
+        if (!conv && c.cg == C && C <= 2 && aligned16(pcm_out)) g.in_mode = C;      // decode: quad store for C = 1 / 2
+        dim3 grid((unsigned)((n_frames + c.fpb - 1) / c.fpb));
+        if (!conv) {
+            if (c.cg < C) FRAD_TRY_LAUNCH(launch_p0_inv_grp2(c, s, in, pcm_out, tb, g));     // whole-row two-pass kernel
+            FRAD_TRY_LAUNCH(launch_p0_inv_pers(c, s, in, pcm_out, tb, g));
+        } else if ((c.log2m == 9 || c.log2m == 10) && C <= 2) {
+            // every store converts, and the kernel is the one frad_p0_digital would run on an aligned float64 buffer (the result
+            // must equal from_f64 of ITS samples bit for bit).  Only the wave kernel's geometries are left to the caller: its
+            // converting twin (k_p0_inv_wave_pcm: s16 / s32 / f32) was tried first, the other formats take the second pass.
+            if (p0_inv_wave_takes(g, ai)) return 1;
+            if (c.cg == C) g.in_mode = C;                     // (what the float64 path sets for an aligned buffer: the unit kernels ask for it)
+            FRAD_TRY_LAUNCH(launch_p0_inv_pers(c, s, in, pcm_out, tb, g));
+            g.in_mode = 0;
+        } else if (c.cg < C) {
+            FRAD_TRY_LAUNCH(launch_p0_inv_grp2(c, s, in, pcm_out, tb, g));
+        }
+        FRAD_TRY_LAUNCH(launch_p0_inv(c, grid, s, in, pcm_out, tb, g, ai));
+        return FRAD_E_UNSUPPORTED;
+    }
+    FRAD_TRY_LAUNCH(launch_p0_inv_mixed(s, in, pcm_out, g, ai));
+    FRAD_TRY_LAUNCH(launch_p0_inv_blue(s, in, pcm_out, g, ai));
+    if (g.fpc > 0) return 1;
+    const size_t per_frame = 2 * (size_t)N * C * 8;
+    if (per_frame > (size_t)kLdsBytes) return conv ? 1 : global_p0_digital(in, pcm_out, g, flags, s);   // (workspace path: float64 rows)
+    DirectTable d; rc = get_direct(N, d);
+    if (rc != FRAD_OK) return rc;
+    g.fpb = direct_fpb(n_frames, C, per_frame);
+    const size_t lds = per_frame * (size_t)g.fpb;
+    const long long nblk = (n_frames + g.fpb - 1) / g.fpb;
+    if (nblk > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
+    allow_lds(k_p0_inv_direct<0>, lds);
+    hipLaunchKernelGGL(k_p0_inv_direct<0>, dim3((unsigned)nblk), dim3((unsigned)direct_threads(N)), lds, s, in, pcm_out, d.ct, g, ai);
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
 int p0_digital_impl(const void* payload, int64_t payload_stride, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
-                    uint32_t flags, double* pcm_out, void* stream, int fpc, long long clip_stride, int out_dtype = FRAD_PCM_F64LE);
+                    uint32_t flags, double* pcm_out, void* stream, int fpc, long long clip_stride, int out_dtype = FRAD_PCM_F64LE) {
+    const bool conv = out_dtype != FRAD_PCM_F64LE;            // the store converts (one-shot / channel-group / mixed-radix / Bluestein / direct kernels)
+    if (conv && fpc > 0) return 1;
+    int rc = check_common(payload, pcm_out, n_frames, N, C, bits);
+    if (rc != FRAD_OK) return rc;
+    if (n_frames == 0) return FRAD_OK;
+    if (payload_stride < (int64_t)frad_payload_bytes(N, C, bits)) return FRAD_E_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Geom g = make_geom(n_frames, N, C, N, payload_stride, bits, flags, FRAD_PCM_F64LE);
+    g.fpc = fpc; g.clip_stride = clip_stride;
+    if (conv) { g.dtype = out_dtype; g.raw_be = (flags & FRAD_RAW_BE_INTS) ? 1 : 0; }
+    const int ai = (aligned16(payload) && payload_stride % 16 == 0) ? 1 : 0;
+    const unsigned char* in = static_cast<const unsigned char*>(payload);
+    const int aout = (aligned16(pcm_out) && (fpc == 0 || ((clip_stride * C) * 8) % 16 == 0)) ? 1 : 0;
+    if (!conv) FRAD_TRY_LAUNCH(launch_p0_inv_wave(s, in, pcm_out, g, ai, aout));
+    rc = p0_inv_flat(in, pcm_out, g, ai, conv, flags, s);
+    if (rc != 1 || fpc == 0) return rc;
+    // clips through a kernel without clip addressing: the flat batch decodes into a dense scratch, one strided copy scatters it
+    const size_t row = (size_t)fpc * N * C * 8;
+    Scratch ws(s);
+    rc = ws.alloc(row * (size_t)(n_frames / fpc));
+    if (rc != FRAD_OK) return rc;
+    rc = p0_digital_impl(payload, payload_stride, n_frames, N, C, bits, flags, ws.as<double>(), stream, 0, 0);
+    if (rc != FRAD_OK) return rc;
+    FRAD_HIPCHK(hipMemcpy2DAsync(pcm_out, (size_t)clip_stride * C * 8, ws.p, row, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
+    return FRAD_OK;
+}
+
 }  // namespace
 namespace frad {
 // frad_p0_digital with the decoder's output conversion applied by the kernel's own store (frad_epilogue.hip: frad_p0_digital_pcm).
@@ -535,97 +589,3 @@ int frad_p0_digital_clips(const void* payload, int64_t payload_stride, int64_t n
 }
 
 }  // extern "C"
-namespace {
-
-int p0_digital_impl(const void* payload, int64_t payload_stride, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
-                    uint32_t flags, double* pcm_out, void* stream, int fpc, long long clip_stride, int out_dtype) {
-    const bool conv = out_dtype != FRAD_PCM_F64LE;            // the store converts (one-shot / channel-group / mixed-radix / Bluestein / direct kernels)
-    if (conv && fpc > 0) return 1;
-    int rc = check_common(payload, pcm_out, n_frames, N, C, bits);
-    if (rc != FRAD_OK) return rc;
-    if (n_frames == 0) return FRAD_OK;
-    if (payload_stride < (int64_t)frad_payload_bytes(N, C, bits)) return FRAD_E_INVALID;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Geom g = make_geom(n_frames, N, C, N, payload_stride, bits, flags, FRAD_PCM_F64LE);
-    g.fpc = fpc; g.clip_stride = clip_stride;
-    if (conv) { g.dtype = out_dtype; g.raw_be = (flags & FRAD_RAW_BE_INTS) ? 1 : 0; }
-    const int ai = (aligned16(payload) && payload_stride % 16 == 0) ? 1 : 0;
-    const unsigned char* in = static_cast<const unsigned char*>(payload);
-    const int aout = (aligned16(pcm_out) && (fpc == 0 || ((clip_stride * C) * 8) % 16 == 0)) ? 1 : 0;
-    if (!conv && launch_p0_inv_wave(s, in, pcm_out, g, ai, aout, unit_neg)) { HIPCHK(hipGetLastError()); return FRAD_OK; }
-    const FastCfg c = fast_cfg(N, C, false);
-    if (fpc > 0 && c.ok) {
-        // clips through a kernel without clip addressing: the flat batch decodes into a dense scratch, one strided copy scatters it
-        const size_t row = (size_t)fpc * N * C * 8;
-        StreamScratch ws{s};
-        if (hipMallocAsync(&ws.p, row * (size_t)(n_frames / fpc), s) != hipSuccess) return FRAD_E_NOMEM;
-        rc = p0_digital_impl(payload, payload_stride, n_frames, N, C, bits, flags, static_cast<double*>(ws.p), stream, 0, 0);
-        if (rc != FRAD_OK) return rc;
-        HIPCHK(hipMemcpy2DAsync(pcm_out, (size_t)clip_stride * C * 8, ws.p, row, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
-        return FRAD_OK;
-    }
-    if (c.ok) {
-        Tables tb; rc = get_tables(c.log2m, false, tb);
-        if (rc != FRAD_OK) return rc;
-        // (12-bit pairs may straddle channel groups here: unpacking only reads them; the packing side refuses that)
-        g.fpb = c.fpb; g.cg = c.cg;
-        if (c.cg == C && ai && C <= 2 && ((long long)N * C) % 32 == 0) g.cc_fast = C;
-        if (!conv && c.cg == C && C <= 2 && aligned16(pcm_out)) g.in_mode = C;      // decode: quad store for C = 1 / 2
-        dim3 grid((unsigned)((n_frames + c.fpb - 1) / c.fpb));
-        if (conv) {
-            // every store converts, and the kernel is the one frad_p0_digital would run on an aligned float64 buffer (the result
-            // must equal from_f64 of ITS samples bit for bit).  Only the wave kernel's geometries are left to the caller: its
-            // converting twin (k_p0_inv_wave_pcm: s16 / s32 / f32) was tried first, the other formats take the second pass.
-            if ((c.log2m == 9 || c.log2m == 10) && C <= 2) {
-                if (p0_inv_wave_takes(g, ai, unit_neg)) return 1;
-                if (c.cg == C) g.in_mode = C;                 // (what the float64 path sets for an aligned buffer: the unit kernels ask for it)
-                if (launch_p0_inv_pers(c, s, in, pcm_out, tb, g)) { HIPCHK(hipGetLastError()); return FRAD_OK; }
-                g.in_mode = 0;
-            } else if (c.cg < C && launch_p0_inv_grp2(c, s, in, pcm_out, tb, g)) { HIPCHK(hipGetLastError()); return FRAD_OK; }
-            rc = launch_p0_inv(c, grid, s, in, pcm_out, tb, g, ai);
-            if (rc != FRAD_OK) return rc;
-        } else if (c.cg < C && launch_p0_inv_grp2(c, s, in, pcm_out, tb, g)) {
-            // whole-row two-pass kernel took it
-        } else if (!launch_p0_inv_pers(c, s, in, pcm_out, tb, g)) {
-            rc = launch_p0_inv(c, grid, s, in, pcm_out, tb, g, ai);
-            if (rc != FRAD_OK) return rc;
-        }
-    } else {
-        {
-            const int rm = launch_p0_inv_mixed(s, in, pcm_out, g, ai, unit_neg);
-            if (rm < 0) { if (rm == FRAD_E_HIP) g_last_hip = mixed_last_hip_error(); return rm; }
-            if (rm == 1) return FRAD_OK;
-        }
-        const int r = launch_p0_inv_blue(s, in, pcm_out, g, ai);
-        if (r < 0) { if (r == FRAD_E_HIP) g_last_hip = blue_last_hip_error(); return r; }
-        if (r == 1) { HIPCHK(hipGetLastError()); return FRAD_OK; }
-        if (fpc > 0) {                                       // (Bluestein did not take it) flat batch into a scratch, then scatter
-            const size_t row = (size_t)fpc * N * C * 8;
-            StreamScratch ws{s};
-            if (hipMallocAsync(&ws.p, row * (size_t)(n_frames / fpc), s) != hipSuccess) return FRAD_E_NOMEM;
-            rc = p0_digital_impl(payload, payload_stride, n_frames, N, C, bits, flags, static_cast<double*>(ws.p), stream, 0, 0);
-            if (rc != FRAD_OK) return rc;
-            HIPCHK(hipMemcpy2DAsync(pcm_out, (size_t)clip_stride * C * 8, ws.p, row, row, (size_t)(n_frames / fpc), hipMemcpyDeviceToDevice, s));
-            return FRAD_OK;
-        }
-        const size_t per_frame = 2 * (size_t)N * C * 8;
-        if (per_frame > (size_t)kLdsBytes) {
-            if (conv) return 1;                              // (workspace path: float64 rows)
-            const int r = global_p0_digital(in, pcm_out, g, flags, s);
-            if (r == FRAD_E_HIP) g_last_hip = global_last_hip_error();
-            return r;
-        }
-        DirectTable d; rc = get_direct(N, d);
-        if (rc != FRAD_OK) return rc;
-        g.fpb = direct_fpb(n_frames, C, per_frame);
-        const size_t lds = per_frame * (size_t)g.fpb;
-        const long long nblk = (n_frames + g.fpb - 1) / g.fpb;
-        if (nblk > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
-        allow_lds(k_p0_inv_direct<0>, lds);
-        hipLaunchKernelGGL(k_p0_inv_direct<0>, dim3((unsigned)nblk), dim3((unsigned)direct_threads(N)), lds, s, in, pcm_out, d.ct, g, ai);
-    }
-    HIPCHK(hipGetLastError());
-    return FRAD_OK;
-}
-
-}  // namespace

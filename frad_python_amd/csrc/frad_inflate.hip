@@ -24,6 +24,7 @@
 // symbols 30-31, a distance beyond the bytes produced, and input that ends before the final block's end-of-block are all
 // status 1.  Bytes after the final block are ignored.  Status 2: the output would not fit the row.
 #include "frad_common.hpp"
+#include "frad_host.hpp"
 #include "../../include/frad_hip.h"
 
 namespace frad {
@@ -381,10 +382,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
     if (lane == 0) { status[f] = st; out_bytes[f] = st == 0 ? pos : 0; }
 }
 
-thread_local int g_inf_hip = 0;
-
 }  // namespace
-int inflate_last_hip_error() { return g_inf_hip; }
 }  // namespace frad
 
 using namespace frad;
@@ -394,7 +392,7 @@ extern "C" int frad_inflate_raw(const void* src, const int64_t* src_offsets, int
     if (n_frames < 0) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!src || !src_offsets || !dst || !dst_bytes || !status) return FRAD_E_INVALID;
-    if (dst_stride < 16 || (dst_stride & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) return FRAD_E_INVALID;
+    if (dst_stride < 16 || (dst_stride & 15) || !aligned16(dst)) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL) return FRAD_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool ring = dst_stride > IF_RING;
@@ -407,7 +405,6 @@ extern "C" int frad_inflate_raw(const void* src, const int64_t* src_offsets, int
         hipLaunchKernelGGL(k_inflate<false>, dim3((unsigned)n_frames), dim3(64), lds, s, static_cast<const unsigned char*>(src),
                            reinterpret_cast<const long long*>(src_offsets), static_cast<unsigned char*>(dst), (long long)dst_stride,
                            reinterpret_cast<long long*>(dst_bytes), status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_inf_hip = (int)e; return FRAD_E_HIP; }
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

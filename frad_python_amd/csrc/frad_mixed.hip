@@ -428,7 +428,6 @@ __global__ void __launch_bounds__(256) k_gm_radix_unpack(const cx<double>* __res
 
 // ---- host: geometry, tables ------------------------------------------------------------------------------------------
 constexpr size_t kLds = 160 * 1024;
-thread_local int g_mixed_hip = 0;
 std::mutex g_mixed_mu;
 struct MixedDev { cx<double>* tw2 = nullptr; cx<double>* post = nullptr; };
 std::map<std::pair<int, int>, MixedDev> g_mixed;             // (device, N)
@@ -448,11 +447,10 @@ bool mixed_geometry(int N, int& r, int& log2p, int max_log2p = 10) {
     return false;
 }
 
-int mixed_tables(int N, unit_root_fn unit, MixedTab& mt, int max_log2p = 10) {
+int mixed_tables(int N, MixedTab& mt, int max_log2p = 10) {
     int r = 0, log2p = 0;
     if (!mixed_geometry(N, r, log2p, max_log2p)) return 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FRAD_E_HIP;
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     Tables t;
     const int rc = get_tables(log2p, false, t);
     if (rc != FRAD_OK) return rc;
@@ -464,23 +462,22 @@ int mixed_tables(int N, unit_root_fn unit, MixedTab& mt, int max_log2p = 10) {
         std::vector<cx<double>> tw2((size_t)(r - 1) * P), post(2 * ((size_t)M / 2 + 1));
         for (int b = 1; b < r; ++b)
             for (int k1 = 0; k1 < P; ++k1) {
-                long double re, im; unit(2LL * b * k1, M, re, im);            // W_M^(b k1) = exp(-i pi 2 b k1 / M)
+                long double re, im; unit_root(2LL * b * k1, M, re, im);         // W_M^(b k1) = exp(-i pi 2 b k1 / M)
                 tw2[(size_t)(b - 1) * P + k1] = cx<double>{(double)re, (double)im};
             }
         for (int k = 0; k <= M / 2; ++k) {
             long double re, im;
-            unit(k, 2LL * N, re, im);                                         // w_k = exp(-i pi k / 2N)
+            unit_root(k, 2LL * N, re, im);                                    // w_k = exp(-i pi k / 2N)
             post[2 * k] = cx<double>{(double)re, (double)im};
-            unit((long long)N + 5LL * k, 2LL * N, re, im);                    // g_k = exp(-i pi (1/2 + 5k/2N))
+            unit_root((long long)N + 5LL * k, 2LL * N, re, im);               // g_k = exp(-i pi (1/2 + 5k/2N))
             post[2 * k + 1] = cx<double>{(double)re, (double)im};
         }
         MixedDev d;
         if (hipMalloc(reinterpret_cast<void**>(&d.tw2), tw2.size() * sizeof(cx<double>)) != hipSuccess) return FRAD_E_NOMEM;
         if (hipMalloc(reinterpret_cast<void**>(&d.post), post.size() * sizeof(cx<double>)) != hipSuccess) { (void)hipFree(d.tw2); return FRAD_E_NOMEM; }
-        if (hipMemcpy(d.tw2, tw2.data(), tw2.size() * sizeof(cx<double>), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d.post, post.data(), post.size() * sizeof(cx<double>), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d.tw2); (void)hipFree(d.post); return FRAD_E_HIP;
-        }
+        hipError_t e = hipMemcpy(d.tw2, tw2.data(), tw2.size() * sizeof(cx<double>), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d.post, post.data(), post.size() * sizeof(cx<double>), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d.tw2); (void)hipFree(d.post); FRAD_HIPCHK(e); }
         it = g_mixed.emplace(key, d).first;
     }
     mt.tw2 = it->second.tw2; mt.post = it->second.post; mt.twp = static_cast<const cx<double>*>(t.tw); mt.r = r; mt.log2p = log2p;
@@ -495,76 +492,73 @@ void mixed_clear() {
     for (auto& kv : g_mixed) { (void)hipFree(kv.second.tw2); (void)hipFree(kv.second.post); }
     g_mixed.clear();
 }
-int mixed_last_hip_error() { return g_mixed_hip; }
-int mixed_prepare(int N, unit_root_fn unit) { MixedTab mt; const int r = mixed_tables(N, unit, mt); return r < 0 ? r : FRAD_OK; }
-
-#define MCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_mixed_hip = (int)e_; return FRAD_E_HIP; } } while (0)
+int mixed_prepare(int N) { MixedTab mt; const int r = mixed_tables(N, mt); return r < 0 ? r : FRAD_OK; }
 
 // 1 = launched, 0 = not this family's geometry (the caller goes on to Bluestein / the direct kernels), < 0 = FRAD_E_*
 int launch_p0_fwd_mixed(int lg, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* absmax, const Geom& g,
-                        int aligned_in, int aligned_out, unit_root_fn unit) {
+                        int aligned_in, int aligned_out) {
     if (mixed_off() || g.n_frames > 0x7fffffffLL) return 0;
     const size_t lds = 2 * (size_t)g.N * g.C * 8;
     if (lds > kLds) return 0;
     MixedTab mt;
-    const int r = mixed_tables(g.N, unit, mt);
+    const int r = mixed_tables(g.N, mt);
     if (r <= 0) return r;
-    if (absmax) MCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)g.n_frames, s));     // atomicMax target
+    if (absmax) FRAD_HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)g.n_frames, s));     // atomicMax target
     Geom gg = g; gg.fpb = 1;
     const dim3 grid((unsigned)g.n_frames), blk(256);
 #define GO(LGV) do { allow_lds(k_p0_fwd_mixed<LGV>, lds); hipLaunchKernelGGL((k_p0_fwd_mixed<LGV>), grid, blk, lds, s, pcm, pay, absmax, gg, mt, aligned_in, aligned_out); } while (0)
     switch (lg) { case 0: GO(0); break; case 1: GO(1); break; case 2: GO(2); break; default: GO(3); break; }
 #undef GO
-    MCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return 1;
 }
 
-int launch_p0_inv_mixed(hipStream_t s, const unsigned char* pay, double* out, const Geom& g, int aligned_in, unit_root_fn unit) {
+int launch_p0_inv_mixed(hipStream_t s, const unsigned char* pay, double* out, const Geom& g, int aligned_in) {
     if (mixed_off() || g.n_frames > 0x7fffffffLL) return 0;
     const size_t lds = 2 * (size_t)g.N * g.C * 8;
     if (lds > kLds) return 0;
     MixedTab mt;
-    const int r = mixed_tables(g.N, unit, mt);
+    const int r = mixed_tables(g.N, mt);
     if (r <= 0) return r;
     Geom gg = g; gg.fpb = 1;
     allow_lds(k_p0_inv_mixed<0>, lds);
     hipLaunchKernelGGL(k_p0_inv_mixed<0>, dim3((unsigned)g.n_frames), dim3(256), lds, s, pay, out, gg, mt, aligned_in);
-    MCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return 1;
 }
 
 int launch_p1_fwd_mixed(int lg, hipStream_t s, const unsigned char* pcm, int32_t* q, int32_t* tq, const Geom& g, const P1Tables& tb,
-                        int aligned_in, unit_root_fn unit) {
+                        int aligned_in) {
     if (mixed_off() || g.n_frames > 0x7fffffffLL) return 0;
     int cg = g.C;                                             // channels per pass: as many as the LDS holds twice over + the quantiser's scratch
     while (cg > 0 && 2 * (size_t)g.N * cg * 8 + p1_scratch_bytes(cg, g.N) > kLds) --cg;
     if (cg < 1) return 0;
     const size_t lds = 2 * (size_t)g.N * cg * 8 + p1_scratch_bytes(cg, g.N);
     MixedTab mt;
-    const int r = mixed_tables(g.N, unit, mt);
+    const int r = mixed_tables(g.N, mt);
     if (r <= 0) return r;
     Geom gg = g; gg.fpb = 1; gg.cg = cg;
     const dim3 grid((unsigned)g.n_frames), blk(256);
 #define GO(LGV) do { allow_lds(k_p1_fwd_mixed<LGV>, lds); hipLaunchKernelGGL((k_p1_fwd_mixed<LGV>), grid, blk, lds, s, pcm, q, tq, gg, tb, mt, aligned_in); } while (0)
     switch (lg) { case 0: GO(0); break; case 1: GO(1); break; case 2: GO(2); break; default: GO(3); break; }
 #undef GO
-    MCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return 1;
 }
 
-int launch_p1_inv_mixed(hipStream_t s, const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb, unit_root_fn unit) {
+int launch_p1_inv_mixed(hipStream_t s, const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb) {
     if (mixed_off() || g.n_frames > 0x7fffffffLL) return 0;
     int cg = g.C;
     while (cg > 0 && 2 * (size_t)g.N * cg * 8 + p1_scratch_bytes(cg, g.N) > kLds) --cg;
     if (cg < 1) return 0;
     const size_t lds = 2 * (size_t)g.N * cg * 8 + p1_scratch_bytes(cg, g.N);
     MixedTab mt;
-    const int r = mixed_tables(g.N, unit, mt);
+    const int r = mixed_tables(g.N, mt);
     if (r <= 0) return r;
     Geom gg = g; gg.fpb = 1; gg.cg = cg;
     allow_lds(k_p1_inv_mixed<0>, lds);
     hipLaunchKernelGGL(k_p1_inv_mixed<0>, dim3((unsigned)g.n_frames), dim3(256), lds, s, q, tq, out, gg, tb, mt);
-    MCHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return 1;
 }
 
@@ -573,10 +567,10 @@ int launch_p1_inv_mixed(hipStream_t s, const int32_t* q, const int32_t* tq, doub
 // element o of row r goes to out[(r / C) * fstride + (r % C) * cstride + o * ostride] as in k_g_dct (frad_global.hip).
 // 1 = done, 0 = N is not of this family, < 0 = FRAD_E_*
 int global_dct_mixed(bool fwd, const double* in, double* out, void* zw, int N, int C, long long rows, long long fstride, long long cstride,
-                     long long ostride, hipStream_t s, unit_root_fn unit) {
+                     long long ostride, hipStream_t s) {
     if (mixed_off() || rows > 65535) return 0;
     MixedTab mt;
-    const int rc = mixed_tables(N, unit, mt, 13);
+    const int rc = mixed_tables(N, mt, 13);
     if (rc <= 0) return rc;
     const int P = 1 << mt.log2p, M = N / 2;
     cx<double>* z = static_cast<cx<double>*>(zw);
@@ -607,7 +601,7 @@ int global_dct_mixed(bool fwd, const double* in, double* out, void* zw, int N, i
         if (mt.r == 3) GO(3); else if (mt.r == 5) GO(5); else GO(7);
 #undef GO
     }
-    if (hipGetLastError() != hipSuccess) return FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
     return 1;
 }
 

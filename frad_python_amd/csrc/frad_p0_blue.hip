@@ -248,8 +248,6 @@ void unit_ld(long long p, long long q, ld& re, ld& im) {
 struct BlueTable { cx<double>* wconj = nullptr; cx<double>* bhat = nullptr; cx<double>* pw = nullptr; cx<double>* pw2 = nullptr; int log2l = 0; };
 std::mutex g_mu;
 std::map<std::pair<int, int>, BlueTable> g_blue;             // (device, N)
-thread_local int g_last = 0;
-#define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last = (int)e_; return FRAD_E_HIP; } } while (0)
 
 int team_for(int log2l) {
     switch (log2l) { case 8: case 9: case 10: return 64; case 11: return 128; case 12: return 256; case 13: return 512; default: return 0; }
@@ -277,13 +275,13 @@ void host_fft(std::vector<ld>& re, std::vector<ld>& im) {   // in place, forward
 }
 
 int upload(const std::vector<cx<double>>& h, cx<double>** d) {
-    BCHK(hipMalloc(d, h.size() * sizeof(cx<double>)));
-    BCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(cx<double>), hipMemcpyHostToDevice));
+    FRAD_HIPCHK(hipMalloc(d, h.size() * sizeof(cx<double>)));
+    FRAD_HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(cx<double>), hipMemcpyHostToDevice));
     return FRAD_OK;
 }
 
 int get_blue(int N, int log2l, BlueTable& out) {
-    int dev = 0; BCHK(hipGetDevice(&dev));
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_pair(dev, N);
     auto it = g_blue.find(key);
@@ -379,8 +377,6 @@ int tables_for(int N, int C, int bits, bool fwd, BlueCfg& c, BlueTable& t, const
 
 }  // namespace
 
-int blue_last_hip_error() { return g_last; }
-
 int blue_prepare(int N) {
     BlueCfg c; BlueTable t; const cx<double>* tw = nullptr;
     const int r = tables_for(N, 1, 32, true, c, t, &tw);
@@ -393,13 +389,12 @@ void blue_clear() {
     g_blue.clear();
 }
 
-// 1: launched, 0: not applicable (caller falls back to the direct kernels), < 0: error
 int launch_p0_fwd_blue(int lg, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* absmax, Geom g, int aligned_out) {
     if (g.n_frames > 0x7fffffffLL) return 0;
     BlueCfg c; BlueTable t; const cx<double>* tw = nullptr;
     const int r = tables_for(g.N, g.C, g.bits, true, c, t, &tw, (g.dtype >> 3) != 2);
     if (r <= 0) return r;
-    if (absmax) BCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)g.n_frames, s));       // atomicMax target
+    if (absmax) FRAD_HIPCHK(hipMemsetAsync(absmax, 0, sizeof(double) * (size_t)g.n_frames, s));       // atomicMax target
     g.cg = c.cg; g.fpb = 1; g.in_mode = c.whole; g.cc_fast = c.paired;
     dim3 grid((unsigned)g.n_frames);
     switch (c.log2l) {

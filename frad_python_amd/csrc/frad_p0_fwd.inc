@@ -1,5 +1,6 @@
 // frad_p0_fwd.inc -- instantiates k_p0_fwd<FWD_T, LOG2M, LG, MAXT> for LOG2M in [FWD_LO, FWD_HI].
-// Included by frad_p0_fwd_*.hip with FWD_T / FWD_NAME / FWD_LO / FWD_HI defined.
+// Included by frad_p0_fwd_*.hip with FWD_T / FWD_NAME / FWD_LO / FWD_HI defined.  FWD_NAME returns 1 = launched, 0 = this
+// (log2m, lg) is not built here.
 #include "frad_launch.hpp"
 
 namespace frad {
@@ -34,7 +35,7 @@ int fwd_lg(int lg, const FastCfg& c, dim3 grid, hipStream_t s, const unsigned ch
     if constexpr (sizeof(FWD_T) == 4) {               // f16 / f32 PCM only
         if (lg == 1) fwd_one<LOG2M, 1>(c, grid, s, pcm, pay, am, tb, g, ai, ao);
         else if (lg == 2) fwd_one<LOG2M, 2>(c, grid, s, pcm, pay, am, tb, g, ai, ao);
-        else return -2;
+        else return 0;
     } else {
         switch (lg) {
             case 0: fwd_one<LOG2M, 0>(c, grid, s, pcm, pay, am, tb, g, ai, ao); break;
@@ -43,7 +44,7 @@ int fwd_lg(int lg, const FastCfg& c, dim3 grid, hipStream_t s, const unsigned ch
             default: fwd_one<LOG2M, 3>(c, grid, s, pcm, pay, am, tb, g, ai, ao); break;
         }
     }
-    return 0;
+    return 1;
 }
 
 }  // namespace
@@ -51,10 +52,10 @@ int fwd_lg(int lg, const FastCfg& c, dim3 grid, hipStream_t s, const unsigned ch
 int FWD_NAME(int lg, const FastCfg& c, dim3 grid, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* am,
              const Tables& tb, const Geom& g, int ai, int ao) {
     switch (c.log2m) {
-#define FRAD_CASE(L) case L: if constexpr (L >= FWD_LO && L <= FWD_HI) return fwd_lg<L>(lg, c, grid, s, pcm, pay, am, tb, g, ai, ao); else return -2;
+#define FRAD_CASE(L) case L: if constexpr (L >= FWD_LO && L <= FWD_HI) return fwd_lg<L>(lg, c, grid, s, pcm, pay, am, tb, g, ai, ao); else return 0;
         FRAD_CASE(6) FRAD_CASE(7) FRAD_CASE(8) FRAD_CASE(9) FRAD_CASE(10) FRAD_CASE(11) FRAD_CASE(12) FRAD_CASE(13)
 #undef FRAD_CASE
-        default: return -2;
+        default: return 0;
     }
 }
 

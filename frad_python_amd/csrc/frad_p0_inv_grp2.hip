@@ -238,7 +238,7 @@ int launch_p0_inv_grp2(const FastCfg& c, hipStream_t s, const unsigned char* pay
     if (tune("FRAD_TUNE_NO_GRP2")) return 0;                                       // A/B knob, not part of the ABI
     if (g.C != 2 * c.cg || g.n_frames > 0x7fffffffLL) return 0;
     const bool conv = g.dtype != 22;                          // not FRAD_PCM_F64LE: the store converts (element stores: no alignment asked of `out`)
-    if ((reinterpret_cast<uintptr_t>(pay) & 15) || (g.payload_stride & 15) || (!conv && (reinterpret_cast<uintptr_t>(out) & 15))) return 0;
+    if (!aligned16(pay) || (g.payload_stride & 15) || (!conv && !aligned16(out))) return 0;
     const cx<double>* tw = static_cast<const cx<double>*>(tb.tw);
     const cx<double>* post = static_cast<const cx<double>*>(tb.post);
     dim3 grid((unsigned)g.n_frames);

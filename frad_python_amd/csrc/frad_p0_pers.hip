@@ -102,9 +102,8 @@ bool plan_b() { const char* e = tune("FRAD_TUNE_PERS_PLAN"); return e && (e[0] =
 }  // namespace
 
 // Host image of the LDS table blob (PersLayout<PL>): pass tables in lane-linear order, then w_k, g_k.
-// `unit(p, q, re, im)` must return exp(-i pi p / q).
 template <typename T, typename PL>
-static void fill_blob(std::vector<unsigned char>& bytes, void (*unit)(long long, long long, long double&, long double&)) {
+static void fill_blob(std::vector<unsigned char>& bytes) {
     using L = PersLayout<PL>;
     constexpr int M = 1 << PL::LOG2M, N = 2 * M, TEAM = PL::TEAM;
     std::vector<cx<T>> out(L::SLOTS, cx<T>{0, 0});
@@ -115,7 +114,7 @@ static void fill_blob(std::vector<unsigned char>& bytes, void (*unit)(long long,
             for (int j = 1; j < R; ++j)
                 for (int kk = 0; kk < KW; ++kk) {
                     const long long k = (kk + (long long)nb * TEAM) & (NS - 1);
-                    long double re, im; unit(2 * j * k, (long long)NS * R, re, im);      // W_{NS R}^{j k}
+                    long double re, im; unit_root(2 * j * k, (long long)NS * R, re, im);      // W_{NS R}^{j k}
                     out[off + (nb * (R - 1) + (j - 1)) * KW + kk] = cx<T>{(T)re, (T)im};
                 }
     };
@@ -124,26 +123,24 @@ static void fill_blob(std::vector<unsigned char>& bytes, void (*unit)(long long,
     pass(L::OFF4, PL::R4, L::NS4);
     for (int k = 0; k <= M / 2; ++k) {
         long double re, im;
-        unit(k, 2LL * N, re, im); out[L::OFFP + k] = cx<T>{(T)re, (T)im};
-        unit((long long)N + 5LL * k, 2LL * N, re, im); out[L::OFFP + M / 2 + 1 + k] = cx<T>{(T)re, (T)im};
+        unit_root(k, 2LL * N, re, im); out[L::OFFP + k] = cx<T>{(T)re, (T)im};
+        unit_root((long long)N + 5LL * k, 2LL * N, re, im); out[L::OFFP + M / 2 + 1 + k] = cx<T>{(T)re, (T)im};
     }
     bytes.assign((unsigned char*)out.data(), (unsigned char*)(out.data() + out.size()));
 }
 // blob `which` (0 = plan A, 1 = plan B) for (log2m, f32); returns its size, 0 when there is none
-size_t pers_blob_build(int log2m, bool f32, int which, std::vector<unsigned char>& bytes,
-                       void (*unit)(long long, long long, long double&, long double&)) {
+size_t pers_blob_build(int log2m, bool f32, int which, std::vector<unsigned char>& bytes) {
     bytes.clear();
     if (log2m == 10 && !f32) {
-        if (which == 0) fill_blob<double, PlanA10>(bytes, unit);
-        else if (which == 1) fill_blob<double, PlanB10>(bytes, unit);
-        else fill_blob<double, PlanI10>(bytes, unit);
+        if (which == 0) fill_blob<double, PlanA10>(bytes);
+        else if (which == 1) fill_blob<double, PlanB10>(bytes);
+        else fill_blob<double, PlanI10>(bytes);
     }
-    else if (log2m == 11 && f32 && which == 0) fill_blob<float, PlanA11>(bytes, unit);
-    else if (log2m == 9 && !f32 && which == 0) fill_blob<double, PlanA9>(bytes, unit);
+    else if (log2m == 11 && f32 && which == 0) fill_blob<float, PlanA11>(bytes);
+    else if (log2m == 9 && !f32 && which == 0) fill_blob<double, PlanA9>(bytes);
     return bytes.size();
 }
 
-// returns 1 when the persistent kernel took the launch, 0 when the geometry is not one of its own
 int launch_p0_fwd_pers(bool f32, int lg, const FastCfg& c, hipStream_t s, const unsigned char* pcm, unsigned char* pay,
                        double* am, const Tables& tb, Geom g, int ao) {
     if (disabled() || tb.blob == nullptr || c.cg != g.C || g.in_mode == 0 || g.n_valid != g.N || g.C > 8) return 0;
@@ -173,7 +170,6 @@ int launch_p0_fwd_pers(bool f32, int lg, const FastCfg& c, hipStream_t s, const 
         return 1;
     }
     if (n1024) return 0;                                      // the block-barrier variant is not built for N = 1024
-    if (am != nullptr && hipMemsetAsync(am, 0, sizeof(double) * (size_t)g.n_frames, s) != hipSuccess) return 0;
     const bool pb = !f32 && plan_b() && tb.blob_b != nullptr && lg <= 2;
     const int team = f32 ? PlanA11::TEAM : pb ? PlanB10::TEAM : PlanA10::TEAM, M = 1 << c.log2m;
     const int cpt = (int)(((long long)g.N << lg) / (16 * team));
@@ -185,6 +181,7 @@ int launch_p0_fwd_pers(bool f32, int lg, const FastCfg& c, hipStream_t s, const 
     const size_t lds = tbytes + (size_t)teams * M * (f32 ? 8 : 16);
     const long long ngroups = (g.n_frames + g.fpb - 1) / g.fpb;
     if (ngroups > 0x7fffffffLL) return 0;
+    if (const int rc = zero_absmax(am, g.n_frames, s)) return rc;        // (the block-barrier kernels accumulate with atomicMax)
     const long long cap = (long long)cu_count() * blocks_per_cu();
     const int grid = (int)(ngroups < cap ? ngroups : cap);
     const int ng = (int)ngroups;

@@ -27,7 +27,6 @@ int wave_stagger() { static const int st = [] { const char* e = tune("FRAD_TUNE_
 
 std::mutex g_wave_mu;
 std::map<int, void*> g_wave_blob;                    // device -> LDS image of WaveLayout
-int g_wave_hip = 0;
 
 template <int LG, int CC, int BITS>
 void go_fwd_wave(const void* blob, int grid, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* am, const Geom& g) {
@@ -88,17 +87,17 @@ void go_inv_wave_bits(const void* blob, int grid, hipStream_t s, const unsigned 
 
 }  // namespace
 
-// Host image of WaveLayout.  `unit(p, q, re, im)` returns exp(-i pi p / q) (long double, exact octant symmetry).
-void wave_blob_build(std::vector<unsigned char>& bytes, void (*unit)(long long, long long, long double&, long double&)) {
+// Host image of WaveLayout, from unit_root (long double, exact octant symmetry).
+void wave_blob_build(std::vector<unsigned char>& bytes) {
     constexpr int N = 2048;
     std::vector<cx<double>> out(WaveLayout::SLOTS);
     for (int k2 = 0; k2 < 32; ++k2)
         for (int l = 0; l < 32; ++l) {
-            long double re, im; unit(2LL * l * k2, 1024, re, im);                 // W_1024^(l k2)
+            long double re, im; unit_root(2LL * l * k2, 1024, re, im);                 // W_1024^(l k2)
             out[WaveLayout::TW1 + k2 * 32 + l] = cx<double>{(double)re, (double)im};
         }
-    auto wk = [&](int k) { long double re, im; unit(k, 2LL * N, re, im); return cx<double>{(double)re, (double)im}; };
-    auto gk = [&](int k) { long double re, im; unit((long long)N + 5LL * k, 2LL * N, re, im); return cx<double>{(double)re, (double)im}; };
+    auto wk = [&](int k) { long double re, im; unit_root(k, 2LL * N, re, im); return cx<double>{(double)re, (double)im}; };
+    auto gk = [&](int k) { long double re, im; unit_root((long long)N + 5LL * k, 2LL * N, re, im); return cx<double>{(double)re, (double)im}; };
     out[WaveLayout::TW1 + 0] = wk(512);                                         // row 0 of TW1 is all ones and never read as such
     out[WaveLayout::TW1 + 1] = gk(512);
     for (int u = 0; u < 16; ++u)
@@ -110,18 +109,19 @@ void wave_blob_build(std::vector<unsigned char>& bytes, void (*unit)(long long, 
     bytes.assign((unsigned char*)out.data(), (unsigned char*)(out.data() + out.size()));
 }
 
-static const void* wave_blob(void (*unit)(long long, long long, long double&, long double&)) {
+// device copy of the blob, one per device; shared with the profile-1 wave kernels (frad_p1_wave.hip)
+const void* wave_blob() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     std::lock_guard<std::mutex> lk(g_wave_mu);
     auto it = g_wave_blob.find(dev);
     if (it != g_wave_blob.end()) return it->second;
     std::vector<unsigned char> bytes;
-    wave_blob_build(bytes, unit);
+    wave_blob_build(bytes);
     void* d = nullptr;
     hipError_t e = hipMalloc(&d, bytes.size());
     if (e == hipSuccess) e = hipMemcpy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { g_wave_hip = (int)e; return nullptr; }
+    if (e != hipSuccess) { last_hip_slot() = (int)e; return nullptr; }
     g_wave_blob[dev] = d;
     return d;
 }
@@ -143,12 +143,11 @@ extern "C" int frad_debug_wave_stamps(unsigned long long* out, int reset) {
 bool wave_geometry(int N, int C, int bits) { return N == 2048 && (C == 1 || C == 2) && (bits == 16 || bits == 32 || bits == 64); }
 
 // 1 = launched, 0 = not this kernel's geometry (caller falls back to the unit / one-shot kernels)
-int launch_p0_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* am, const Geom& g, int ai, int ao,
-                       void (*unit)(long long, long long, long double&, long double&)) {
+int launch_p0_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, unsigned char* pay, double* am, const Geom& g, int ai, int ao) {
     if (wave_disabled() || !wave_geometry(g.N, g.C, g.bits) || !ai || !ao || g.n_valid != g.N) return 0;
     if (g.fpc > 0 && lg != 1) return 0;                       // clip batches: the 16-bit PCM variant only (others: strided copy + flat batch)
     if ((g.dtype >> 3) == 2 && ((g.dtype >> 1) & 3) <= 2) return 0;   // f16 / f32 PCM: float32 compute stays with the f32 kernels
-    const void* blob = wave_blob(unit);
+    const void* blob = wave_blob();
     if (blob == nullptr) return 0;
     const long long units = g.C == 2 ? g.n_frames : (g.n_frames + 1) / 2;
     const long long nb = (units + kWaveWaves - 1) / kWaveWaves, cap = wave_cu_count();
@@ -163,14 +162,14 @@ int launch_p0_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, unsigned
 
 // would launch_p0_inv_wave take this batch into an aligned float64 buffer?  (frad_p0_digital_pcm must convert the samples of the
 // kernel frad_p0_digital runs)
-bool p0_inv_wave_takes(const Geom& g, int ai, unit_root_fn unit) {
-    return !wave_disabled() && wave_geometry(g.N, g.C, g.bits) && ai && !tune("FRAD_TUNE_NO_WAVE_DEC") && wave_blob(unit) != nullptr;
+bool p0_inv_wave_takes(const Geom& g, int ai) {
+    return !wave_disabled() && wave_geometry(g.N, g.C, g.bits) && ai && !tune("FRAD_TUNE_NO_WAVE_DEC") && wave_blob() != nullptr;
 }
 
-int launch_p0_inv_wave(hipStream_t s, const unsigned char* pay, double* out, const Geom& g, int ai, int ao, unit_root_fn unit) {
+int launch_p0_inv_wave(hipStream_t s, const unsigned char* pay, double* out, const Geom& g, int ai, int ao) {
     if (wave_disabled() || !wave_geometry(g.N, g.C, g.bits) || !ai || !ao) return 0;
     if (tune("FRAD_TUNE_NO_WAVE_DEC")) return 0;
-    const void* blob = wave_blob(unit);
+    const void* blob = wave_blob();
     if (blob == nullptr) return 0;
     const long long units = g.C == 2 ? g.n_frames : (g.n_frames + 1) / 2;
     const long long nb = (units + kWaveWaves - 1) / kWaveWaves, cap = wave_cu_count();
@@ -185,7 +184,6 @@ int launch_p0_inv_wave(hipStream_t s, const unsigned char* pay, double* out, con
 
 
 // shared with the profile-1 wave kernels (frad_p1_wave.hip)
-const void* wave_blob_get(unit_root_fn unit) { return wave_blob(unit); }
 int wave_grid(long long units) {
     const long long nb = (units + kWaveWaves - 1) / kWaveWaves, cap = wave_cu_count();
     return (int)(nb < cap ? nb : cap);

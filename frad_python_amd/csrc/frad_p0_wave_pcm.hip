@@ -7,7 +7,7 @@
 
 namespace frad {
 
-const void* wave_blob_get(unit_root_fn unit);
+const void* wave_blob();
 int wave_grid(long long units);
 bool wave_off();
 int wave_stagger_steps();
@@ -32,12 +32,12 @@ bool go_bits(const void* blob, int grid, hipStream_t s, const unsigned char* pay
 }
 }  // namespace
 
-int launch_p0_inv_wave_pcm(hipStream_t s, const unsigned char* pay, void* out, const Geom& g, int ai, int out_dtype, unit_root_fn unit) {
+int launch_p0_inv_wave_pcm(hipStream_t s, const unsigned char* pay, void* out, const Geom& g, int ai, int out_dtype) {
     static const bool off = [] { const char* e = tune("FRAD_TUNE_NO_WAVE_PCM"); return e && e[0] == '1'; }();
-    if (wave_off() || off || g.N != 2048 || (g.C != 2 && g.C != 1) || !ai || (reinterpret_cast<uintptr_t>(out) & 15)) return 0;
+    if (wave_off() || off || g.N != 2048 || (g.C != 2 && g.C != 1) || !ai || !aligned16(out)) return 0;
     if (out_dtype != FRAD_PCM_S16LE && out_dtype != FRAD_PCM_S32LE && out_dtype != FRAD_PCM_F32LE) return 0;
     if (g.bits != 16 && g.bits != 32) return 0;
-    const void* blob = wave_blob_get(unit);
+    const void* blob = wave_blob();
     if (blob == nullptr) return 0;
     Geom gg = g;
     gg.cg = wave_stagger_steps(); gg.fpb = 0;

@@ -14,11 +14,9 @@
 using namespace frad;
 
 namespace frad {
-int p1_digital_out(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_t N, int32_t C, int32_t bits, int32_t srate,
-                   int out_dtype, uint32_t flags, void* out, void* stream);
 int launch_p1_fwd_mixed(int lg, hipStream_t s, const unsigned char* pcm, int32_t* q, int32_t* tq, const Geom& g, const P1Tables& tb,
-                        int aligned_in, unit_root_fn unit);
-int launch_p1_inv_mixed(hipStream_t s, const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb, unit_root_fn unit);
+                        int aligned_in);
+int launch_p1_inv_mixed(hipStream_t s, const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb);
 }
 
 namespace {
@@ -43,15 +41,12 @@ int p1_scale_bits(int bits) {                    // profile1.py:16: unknown dept
     return 16;
 }
 
-thread_local int g_last = 0;
-
 // per-bin band index tables, one per (device, N, snapped rate); a few KiB each, kept for the process lifetime
 std::mutex g_band_mu;
 std::map<std::tuple<int, int, int>, unsigned char*> g_band;
 
 int band_table(int N, int sr, const P1Tables& tb, const unsigned char** out) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FRAD_E_HIP;
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_band_mu);
     auto key = std::make_tuple(dev, N, sr);
     auto it = g_band.find(key);
@@ -63,11 +58,10 @@ int band_table(int N, int sr, const P1Tables& tb, const unsigned char** out) {
     }
     unsigned char* d = nullptr;
     if (hipMalloc(&d, (size_t)N) != hipSuccess) return FRAD_E_NOMEM;
-    if (hipMemcpy(d, host.data(), (size_t)N, hipMemcpyHostToDevice) != hipSuccess) return FRAD_E_HIP;
+    if (const hipError_t e = hipMemcpy(d, host.data(), (size_t)N, hipMemcpyHostToDevice)) { (void)hipFree(d); FRAD_HIPCHK(e); }
     g_band[key] = d; *out = d;
     return FRAD_OK;
 }
-#define P1CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last = (int)e_; return FRAD_E_HIP; } } while (0)
 
 int make_tables(int N, int srate, int bits, double loss_level, P1Tables& tb) {
     const int sr = valid_srate(srate);
@@ -179,22 +173,6 @@ P1Wave wave_tables(const P1Tables& tb, int N) {
     pw.scale = tb.scale; pw.loss = tb.loss; pw.nb_used = tb.nb_used; pw.band_of = tb.band_of; pw.tq_in = nullptr; pw.tq_out = nullptr;
     return pw;
 }
-// the root-of-unity generator the wave table blob is built with (the same values as frad_hip.hip's tables)
-void p1_unit_neg(long long p, long long q, long double& re, long double& im) {
-    const long double PI = 3.14159265358979323846264338327950288419716939937510L;
-    long long r = p % (2 * q); if (r < 0) r += 2 * q;
-    const long long h = q / 2;
-    const int quad = (int)(r / h);
-    const long long rem = r % h;
-    long double c, s;
-    if (4 * rem <= q) { c = cosl(PI * (long double)rem / (long double)q); s = sinl(PI * (long double)rem / (long double)q); }
-    else { c = sinl(PI * (long double)(h - rem) / (long double)q); s = cosl(PI * (long double)(h - rem) / (long double)q); }
-    if (rem == 0) { c = 1.0L; s = 0.0L; }
-    long double C, S;
-    switch (quad) { case 0: C = c; S = s; break; case 1: C = -s; S = c; break; case 2: C = -c; S = -s; break; default: C = s; S = -c; }
-    re = C; im = -S;
-}
-
 Geom p1_geom(long long n_frames, int N, int C, long long stride, int n_valid, int dtype, uint32_t flags) {
     Geom g{};
     g.n_frames = n_frames; g.frame_stride = stride; g.payload_stride = 0; g.N = N; g.C = C; g.bits = 32; g.le = 0;
@@ -223,9 +201,8 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     if (n_frames < 0 || C < 1 || C > 64 || !legal_compact_size(N) || n_valid < 0 || n_valid > N) return FRAD_E_INVALID;
     if (pcm_dtype < 0 || pcm_dtype > 23) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
-    if (!pcm || !q || !tq) return FRAD_E_INVALID;
+    if (!pcm || !q || !tq || !valid_pcm_dtype(pcm_dtype)) return FRAD_E_INVALID;
     const int kind = pcm_dtype >> 3, lg = (pcm_dtype >> 1) & 3;
-    if ((kind == 2 && lg == 0) || (lg == 0 && (pcm_dtype & 1))) return FRAD_E_INVALID;
     P1Tables tb;
     int rc = make_tables(N, srate, bits, loss_level, tb);
     if (rc != FRAD_OK) return rc;
@@ -234,7 +211,7 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     tb.f32 = (kind == 2 && lg <= 2) ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     Geom g = p1_geom(n_frames, N, C, frame_stride, n_valid, pcm_dtype, flags);
-    const int ai = ((reinterpret_cast<uintptr_t>(pcm) & 15u) == 0 && (((frame_stride * C) << lg) % 16 == 0) &&
+    const int ai = (aligned16(pcm) && (((frame_stride * C) << lg) % 16 == 0) &&
                     ((((long long)N * C) << lg) % 16 == 0)) ? 1 : 0;
     const unsigned char* in = static_cast<const unsigned char*>(pcm);
     if (!tb.f32) {
@@ -242,7 +219,7 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
         pw.tq_out = tq;
         const double* dt = deq_table();
         pw.tqh = dt ? dt + 512 : nullptr;
-        if (launch_p1_fwd_wave(lg, s, in, q, g, pw, ai, p1_unit_neg)) { P1CHK(hipGetLastError()); return FRAD_OK; }
+        FRAD_TRY_LAUNCH(launch_p1_fwd_wave(lg, s, in, q, g, pw, ai));
     }
     FastCfg c = fast_cfg(N, C, false);
     if (p1_fast_fits(c, N, C)) {
@@ -280,16 +257,8 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     } else {
         const size_t lds = 2 * (size_t)N * C * 8 + p1_scratch_bytes(C, N);
         if (n_frames > 0x7fffffffLL / C) return FRAD_E_UNSUPPORTED;
-        {                                                    // {160, 192, 224} x 2^n: mixed-radix FFT (frad_mixed.hip)
-            const int r = launch_p1_fwd_mixed(lg, s, in, q, tq, g, tb, ai, p1_unit_neg);
-            if (r < 0) { if (r == FRAD_E_HIP) g_last = mixed_last_hip_error(); return r; }
-            if (r == 1) return FRAD_OK;
-        }
-        if (lds > kLds) {
-            rc = global_p1_analogue(in, q, tq, g, tb, s);
-            if (rc == FRAD_E_HIP) g_last = global_last_hip_error();
-            return rc;
-        }
+        FRAD_TRY_LAUNCH(launch_p1_fwd_mixed(lg, s, in, q, tq, g, tb, ai));    // {160, 192, 224} x 2^n: mixed-radix FFT (frad_mixed.hip)
+        if (lds > kLds) return global_p1_analogue(in, q, tq, g, tb, s);
         DirectTable d; rc = get_direct(N, d);
         if (rc != FRAD_OK) return rc;
         dim3 grid((unsigned)n_frames);
@@ -297,7 +266,7 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
         switch (lg) { case 0: GOD(0); break; case 1: GOD(1); break; case 2: GOD(2); break; default: GOD(3); break; }
 #undef GOD
     }
-    P1CHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -309,9 +278,7 @@ int frad_p1_digital(const int32_t* q, const int32_t* tq, int64_t n_frames, int32
 int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64_t n_frames, int32_t N, int32_t C, int32_t bits,
                   int32_t srate, double* coeffs_out, void* stream) {
     if (n_frames < 0 || C < 1 || C > 64 || !legal_compact_size(N)) return FRAD_E_INVALID;
-    bool depth = false;
-    for (int b : {8, 10, 12, 14, 16, 20, 24}) depth |= b == bits;       // profile2.py:7 DEPTHS (not profile 1's table)
-    if (!depth) return FRAD_E_INVALID;
+    if (!valid_p2_depth(bits)) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!q || !tq || !lpc || !coeffs_out) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL * 64 / C) return FRAD_E_UNSUPPORTED;
@@ -324,7 +291,7 @@ int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64
     const long long blocks = (n_frames * C + 63) / 64;
     hipLaunchKernelGGL(k_p2_synth<0>, dim3((unsigned)blocks), dim3(64), lds, static_cast<hipStream_t>(stream), q, tq, lpc, coeffs_out,
                        (long long)n_frames, N, C, ldexp(1.0, bits - 1), tb.band_of, pe);
-    P1CHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -332,12 +299,8 @@ int frad_p2_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
                      int32_t n_valid, int32_t bits, int32_t srate, double loss_level, uint32_t flags,
                      int32_t* q, int32_t* tq, int32_t* lpc, void* stream) {
     if (n_frames < 0 || C < 1 || C > 64 || !legal_compact_size(N) || n_valid < 0 || n_valid > N || frame_stride < 0) return FRAD_E_INVALID;
-    if (pcm_dtype < 0 || pcm_dtype > 23) return FRAD_E_INVALID;
-    bool depth = false;
-    for (int b : {8, 10, 12, 14, 16, 20, 24}) depth |= b == bits;       // profile2.py:7 DEPTHS
-    if (!depth) return FRAD_E_INVALID;
+    if (!valid_pcm_dtype(pcm_dtype) || !valid_p2_depth(bits)) return FRAD_E_INVALID;
     const int kind = pcm_dtype >> 3, lg = (pcm_dtype >> 1) & 3;
-    if ((kind == 2 && lg == 0) || (lg == 0 && (pcm_dtype & 1))) return FRAD_E_INVALID;
     if (n_frames == 0) return FRAD_OK;
     if (!pcm || !q || !tq || !lpc) return FRAD_E_INVALID;
     if (n_frames > 0x7fffffffLL / C) return FRAD_E_UNSUPPORTED;
@@ -347,22 +310,24 @@ int frad_p2_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     tb.scale = ldexp(1.0, bits - 1);                                       // profile2.py:9-10 (profile 1's depth table does not apply)
     tb.f32 = (kind == 2 && lg <= 2) ? 1 : 0;                               // float32 / float16 PCM: float32 DCT and band statistics
     hipStream_t s = static_cast<hipStream_t>(stream);
-    struct Scratch { hipStream_t s; void* p = nullptr; ~Scratch() { if (p) (void)hipFreeAsync(p, s); } } plane{s}, padded{s};
+    Scratch plane(s), padded(s);
     const size_t item = (size_t)1 << lg;
     const void* src = pcm;
     long long stride = frame_stride;
     if (n_valid < N) {                                                     // frames shorter than N: zero-padded copies (profile2.py:20)
         const size_t row = (size_t)N * C * item;
-        if (hipMallocAsync(&padded.p, row * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
-        P1CHK(hipMemsetAsync(padded.p, 0, row * (size_t)n_frames, s));
+        rc = padded.alloc(row * (size_t)n_frames);
+        if (rc != FRAD_OK) return rc;
+        FRAD_HIPCHK(hipMemsetAsync(padded.p, 0, row * (size_t)n_frames, s));
         if (n_valid > 0)
-            P1CHK(hipMemcpy2DAsync(padded.p, row, pcm, (size_t)frame_stride * C * item, (size_t)n_valid * C * item, (size_t)n_frames,
+            FRAD_HIPCHK(hipMemcpy2DAsync(padded.p, row, pcm, (size_t)frame_stride * C * item, (size_t)n_valid * C * item, (size_t)n_frames,
                                    hipMemcpyDeviceToDevice, s));
         src = padded.p; stride = N;
     }
     // stage A: the float64 DCT plane (norm='forward') -- profile 0's transform at 64-bit little-endian storage
     const size_t pbytes = (size_t)N * C * 8;
-    if (hipMallocAsync(&plane.p, pbytes * (size_t)n_frames, s) != hipSuccess) return FRAD_E_NOMEM;
+    rc = plane.alloc(pbytes * (size_t)n_frames);
+    if (rc != FRAD_OK) return rc;
     rc = frad_p0_analogue(src, pcm_dtype, n_frames, N, C, stride, 64, FRAD_LITTLE_ENDIAN | (flags & FRAD_RAW_BE_INTS), plane.p,
                           (int64_t)pbytes, nullptr, stream);
     if (rc != FRAD_OK) return rc;
@@ -370,7 +335,7 @@ int frad_p2_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
     const size_t lds = (size_t)p2_analysis_lds(N);
     hipLaunchKernelGGL(k_p2_analysis<0>, dim3((unsigned)(n_frames * C)), dim3(P2_THREADS), lds, s, static_cast<double*>(plane.p), q, tq, lpc,
                        (long long)n_frames, N, C, tb);
-    P1CHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -395,15 +360,16 @@ int p1_digital_out(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_
     if (N == 2048 && C <= 2 && n_frames < 0x7fffffffLL && p1_fast_fits(c, N, C)) {
         // N = 2048, one or two channels: the table-driven wave kernel, then the exact kernel over the frames it marked (a band
         // code outside [0, 256) or |q| >= 256: none in a sane stream).  The list is stream-ordered scratch: count + one slot per frame.
-        struct Redo { hipStream_t s; int* p = nullptr; ~Redo() { if (p) (void)hipFreeAsync(p, s); } } redo{s};
-        if (hipMallocAsync(reinterpret_cast<void**>(&redo.p), sizeof(int) * (size_t)(n_frames + 1), s) != hipSuccess) return FRAD_E_NOMEM;
-        P1CHK(hipMemsetAsync(redo.p, 0, sizeof(int), s));
+        Scratch redo(s);
+        rc = redo.alloc(sizeof(int) * (size_t)(n_frames + 1));
+        if (rc != FRAD_OK) return rc;
+        FRAD_HIPCHK(hipMemsetAsync(redo.p, 0, sizeof(int), s));
         P1Wave pw = wave_tables(tb, N);
         pw.tq_in = tq;
         pw.deq = deq_table();
-        pw.redo = redo.p;
-        if (launch_p1_inv_wave(s, q, pcm_out, g, pw, p1_unit_neg)) {
-            P1CHK(hipGetLastError());
+        pw.redo = redo.as<int>();
+        if (launch_p1_inv_wave(s, q, pcm_out, g, pw)) {
+            FRAD_HIPCHK(hipGetLastError());
             const int M = 1 << c.log2m;
             const size_t lds = (size_t)C * M * 16 + p1_scratch_bytes(C, N);
             Tables t; rc = get_tables(c.log2m, false, t);
@@ -413,8 +379,8 @@ int p1_digital_out(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_
             const cx<double>* tw = static_cast<const cx<double>*>(t.tw); const cx<double>* post = static_cast<const cx<double>*>(t.post);
             const unsigned grid = (unsigned)(n_frames < 256 ? n_frames : 256);
             allow_lds(k_p1_inv_redo<10, 256>, lds);
-            hipLaunchKernelGGL((k_p1_inv_redo<10, 256>), dim3(grid), dim3(threads), lds, s, q, tq, pcm_out, tw, post, gr, tb, redo.p);
-            P1CHK(hipGetLastError());
+            hipLaunchKernelGGL((k_p1_inv_redo<10, 256>), dim3(grid), dim3(threads), lds, s, q, tq, pcm_out, tw, post, gr, tb, redo.as<int>());
+            FRAD_HIPCHK(hipGetLastError());
             return FRAD_OK;
         }
     }
@@ -453,23 +419,14 @@ int p1_digital_out(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_
     } else {
         const size_t lds = 2 * (size_t)N * C * 8 + p1_scratch_bytes(C, N);
         if (n_frames > 0x7fffffffLL / C) return FRAD_E_UNSUPPORTED;
-        {
-            const int r = launch_p1_inv_mixed(s, q, tq, pcm_out, g, tb, p1_unit_neg);
-            if (r < 0) { if (r == FRAD_E_HIP) g_last = mixed_last_hip_error(); return r; }
-            if (r == 1) return FRAD_OK;
-        }
-        if (lds > kLds) {
-            if (conv) return 1;
-            rc = global_p1_digital(q, tq, pcm_out, g, tb, s);
-            if (rc == FRAD_E_HIP) g_last = global_last_hip_error();
-            return rc;
-        }
+        FRAD_TRY_LAUNCH(launch_p1_inv_mixed(s, q, tq, pcm_out, g, tb));
+        if (lds > kLds) return conv ? 1 : global_p1_digital(q, tq, pcm_out, g, tb, s);
         DirectTable d; rc = get_direct(N, d);
         if (rc != FRAD_OK) return rc;
         allow_lds(k_p1_inv_direct<0>, lds);
         hipLaunchKernelGGL(k_p1_inv_direct<0>, dim3((unsigned)n_frames), dim3(256), lds, s, q, tq, pcm_out, d.ct, g, tb);
     }
-    P1CHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 
@@ -488,7 +445,7 @@ int frad_p1_overlap_add(const double* frames, int64_t n_frames, int32_t N, int32
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_p1_ola<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), frames, (long long)n_frames, N, C,
                        cut, prev_tail, ola_out, next_tail);
-    P1CHK(hipGetLastError());
+    FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }
 

@@ -5,7 +5,7 @@
 
 namespace frad {
 
-const void* wave_blob_get(unit_root_fn unit);
+const void* wave_blob();
 int wave_grid(long long units);
 bool wave_off();
 int wave_stagger_steps();
@@ -38,10 +38,10 @@ extern "C" int frad_debug_wave_stamps_p1(unsigned long long* out, int reset) {  
 #endif
 
 // K7.  Needs whole frames (n_valid = N), 16-byte aligned PCM rows (ai), integer or float64 PCM of 2, 4 or 8 bytes.
-int launch_p1_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, int32_t* q, const Geom& g, const P1Wave& pw, int ai, unit_root_fn unit) {
+int launch_p1_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, int32_t* q, const Geom& g, const P1Wave& pw, int ai) {
     if (wave_off() || p1_wave_off() || g.N != 2048 || (g.C != 1 && g.C != 2) || !ai || g.n_valid != g.N || lg < 1) return 0;
     if ((g.dtype >> 3) == 2 && lg <= 2) return 0;              // f16 / f32 PCM: the reference's mixed-precision path (one-shot kernels)
-    if (pw.edge[26] < g.N || (reinterpret_cast<uintptr_t>(q) & 15) || pw.tqh == nullptr) return 0;
+    if (pw.edge[26] < g.N || !aligned16(q) || pw.tqh == nullptr) return 0;
     // the tail's band-energy pass (wave_p1_tail): a run of 32 consecutive bins touches at most three bands and a band spans at
     // most kK7Slots runs -- true for every table rate up to 48 kHz at this frame length
     for (int b = 0; b < 26 && pw.edge[b] < g.N; ++b) {
@@ -51,7 +51,7 @@ int launch_p1_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, int32_t*
     }
     auto band_at = [&](int k) { int b = 0; while (b < 25 && pw.edge[b + 1] <= k) ++b; return b; };
     for (int r = 0; r < g.N / 32; ++r) if (band_at(32 * r + 31) - band_at(32 * r) > 2) return 0;
-    const void* blob = wave_blob_get(unit);
+    const void* blob = wave_blob();
     if (blob == nullptr) return 0;
     Geom gg = g;
     gg.cg = wave_stagger_steps(); gg.fpb = 0; gg.bits = 32; gg.le = 1; gg.payload_stride = (long long)g.N * g.C * 4;
@@ -63,10 +63,10 @@ int launch_p1_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, int32_t*
 }
 
 // K8
-int launch_p1_inv_wave(hipStream_t s, const int32_t* q, double* out, const Geom& g, const P1Wave& pw, unit_root_fn unit) {
+int launch_p1_inv_wave(hipStream_t s, const int32_t* q, double* out, const Geom& g, const P1Wave& pw) {
     if (wave_off() || p1_wave_off() || g.N != 2048 || (g.C != 1 && g.C != 2)) return 0;
-    if ((reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(q) & 3) || pw.edge[26] < g.N || pw.deq == nullptr) return 0;
-    const void* blob = wave_blob_get(unit);
+    if (!aligned16(out) || (reinterpret_cast<uintptr_t>(q) & 3) || pw.edge[26] < g.N || pw.deq == nullptr) return 0;
+    const void* blob = wave_blob();
     if (blob == nullptr) return 0;
     const int grid = wave_grid(g.C == 2 ? g.n_frames : (g.n_frames + 1) / 2);
     Geom gg = g;

@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(256) k_bench_copy(const v4u* __restrict__ src,
 }  // namespace frad
 
 extern "C" int frad_bench_copy(const void* src, void* dst, int64_t nbytes, void* stream) {
-    if (nbytes < 0 || (nbytes & 15) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15)) return FRAD_E_INVALID;
+    if (nbytes < 0 || (nbytes & 15) || !frad::aligned16(src) || !frad::aligned16(dst)) return FRAD_E_INVALID;
     if (nbytes == 0) return FRAD_OK;
     if (!src || !dst) return FRAD_E_INVALID;
     const long long n16 = nbytes / 16;
@@ -33,5 +33,6 @@ extern "C" int frad_bench_copy(const void* src, void* dst, int64_t nbytes, void*
     if (blocks > 256 * 64) blocks = 256 * 64;
     hipLaunchKernelGGL(frad::k_bench_copy, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const frad::v4u*>(src), static_cast<frad::v4u*>(dst), n16);
-    return hipGetLastError() == hipSuccess ? FRAD_OK : FRAD_E_HIP;
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
 }

@@ -161,7 +161,12 @@ inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t
     return hipSuccess;
 }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
-inline hipError_t hipGetLastError() { return hipSuccess; }
+// test hook: the next hipGetLastError() returns this code, once.  An inline variable: one instance for all translation
+// units of the library.  Its setter is exported by the emulator build alone (a weak definition per translation unit, merged
+// by the linker); it is not part of the C-ABI and not declared in frad_hip.h.
+namespace emu { inline hipError_t next_error = hipSuccess; }
+extern "C" __attribute__((weak)) void frad_emu_fail_next(int hip_error) { emu::next_error = hip_error; }
+inline hipError_t hipGetLastError() { const hipError_t e = emu::next_error; emu::next_error = hipSuccess; return e; }
 struct hipDeviceProp_t { size_t maxSharedMemoryPerMultiProcessor = 163840, sharedMemPerBlockOptin = 163840; int multiProcessorCount = 1; };
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { *p = hipDeviceProp_t(); return hipSuccess; }
 struct hipFuncAttributes { int numRegs = 0; };
