@@ -37,11 +37,43 @@ extern "C" int frad_debug_wave_stamps_p1(unsigned long long* out, int reset) {  
 }
 #endif
 
-// K7.  Needs whole frames (n_valid = N), 16-byte aligned PCM rows (ai), integer or float64 PCM of 2, 4 or 8 bytes.
+// The largest |X[k]| 2^(bits - 1) a frame of this PCM type can hold.  The reference's DCT-II is forward-normalised (an average
+// of the samples times cosines), so |X[k]| <= max |pcm| after to_f64: 1 for normalised integers, 2^(w - 1) (signed) or 2^w
+// (unsigned) for big-endian integers that FRAD_RAW_BE_INTS leaves unscaled.  0 = the host knows no bound: float PCM is not clipped.
+static double p1_wave_peak(const Geom& g, double scale) {
+    const int kind = g.dtype >> 3, lg = (g.dtype >> 1) & 3, be = g.dtype & 1;
+    if (kind == 2) return 0.0;
+    if (!(be && g.raw_be)) return scale;
+    return ldexp(scale, (8 << lg) - (kind == 1 ? 1 : 0));
+}
+
+// What K7's float32 decisions can represent (frad_wave.hpp: k7_pow04, k7_band_code, k7_quantise), as a bound on the scaled
+// coefficients |x| <= peak, and so on every band's RMS:
+//   * k7_pow04 refines its float32 seed by Newton steps that multiply with a float32 reciprocal of y^5 ~ (mean square)^2 =
+//     rms^4.  With rms <= peak <= 2^31 that is at most 2^124 and its reciprocal at least 2^-124: both normal float32 numbers.
+//     From rms = 2^32 on, (float)y^5 is +inf, its reciprocal 0, the steps correct nothing and the threshold keeps the seed's
+//     1e-6 -- enough to mis-round a bin within 1e-4 of a tie;
+//   * k7_quantise's exact branch takes a float32 reciprocal of y^4 div^3 ~ |x|^3 <= 2^93: inside float32 a fortiori;
+//   * k7_band_code decides exactly only inside its table of 256 code boundaries.  A band's threshold is at most
+//     max(rms^0.8, floor <= 1) x loss, so peak^0.8 x loss below (e/2)^(255^0.75) ~ 3.1e8 keeps every code <= 255 and the float32
+//     estimate (absolute error ~ 3e-4 there) below the 255.4 at which the table route ends.  At peak = 2^31 that is loss < 10.8.
+// Anything louder -- profile-1 depths beyond 32 bit on normalised PCM, most unscaled big-endian integers (s16be from 24 bit on,
+// every s32be / s64be), extreme loss levels -- goes to the one-shot kernel, whose float64 arithmetic has no such range.
+static bool p1_wave_in_range(const Geom& g, const P1Wave& pw) {
+    static const double kCodeLimit = pow(2.718281828459045 / 2, pow(255.0, 0.75));
+    const double peak = p1_wave_peak(g, pw.scale);
+    if (!(peak > 0.0) || !(peak <= 0x1p31)) return false;
+    const double t = pow(peak, 0.8);
+    return (t > 1.0 ? t : 1.0) * pw.loss < kCodeLimit;
+}
+
+// K7.  Needs whole frames (n_valid = N), 16-byte aligned PCM rows (ai), integer PCM of 2, 4 or 8 bytes whose scaled coefficients
+// stay inside what the kernel's float32 decisions represent (p1_wave_in_range; float64 PCM has no bound, so it never does).
 int launch_p1_fwd_wave(int lg, hipStream_t s, const unsigned char* pcm, int32_t* q, const Geom& g, const P1Wave& pw, int ai) {
     if (wave_off() || p1_wave_off() || g.N != 2048 || (g.C != 1 && g.C != 2) || !ai || g.n_valid != g.N || lg < 1) return 0;
     if ((g.dtype >> 3) == 2 && lg <= 2) return 0;              // f16 / f32 PCM: the reference's mixed-precision path (one-shot kernels)
     if (pw.edge[26] < g.N || !aligned16(q) || pw.tqh == nullptr) return 0;
+    if (!p1_wave_in_range(g, pw)) return 0;
     // the tail's band-energy pass (wave_p1_tail): a run of 32 consecutive bins touches at most three bands and a band spans at
     // most kK7Slots runs -- true for every table rate up to 48 kHz at this frame length
     for (int b = 0; b < 26 && pw.edge[b] < g.N; ++b) {

@@ -420,7 +420,8 @@ __device__ __forceinline__ float k7_rcpf(float v) {
 }
 // r^0.4 = sqrt(r)^0.8 (p1tools.py:30, r = mean of the squared band), float64 to a few ulp without libm (whose constants the
 // compiler hoists out of the frame loop into registers it then spills): float32 seed, two Newton steps on y^5 = r^2, the
-// division inside a step by a float32 reciprocal (it scales a correction of relative size 1e-5 and 1e-11).
+// division inside a step by a float32 reciprocal (it scales a correction of relative size 1e-5 and 1e-11).  That reciprocal is of
+// y^5 ~ r^2 = rms^4: above rms = 2^32 it is 1 / inf = 0 and the steps do nothing, so the launch rule admits rms <= 2^31 only.
 __device__ __forceinline__ double k7_pow04(double r) {
     const float rf = (float)r;
     if (!(rf > 1e-30f)) return 0.0;                           // (far below every absolute threshold of hearing: the floor wins)
@@ -435,8 +436,10 @@ __device__ __forceinline__ double k7_pow04(double r) {
     return y;
 }
 // (int) round(dequant(log(max(t, 1)) / log(e / 2))) (profile1.py:38-40) = the number of table entries tqh[n] <= t: float32
-// estimate, then one exact step either way.  Beyond the table (band RMS above 3e8 in scaled units: not reachable with PCM of
-// 32 bits or fewer at the loss levels the reference offers) the float32 estimate stands.
+// estimate, then one exact step either way.  Beyond the table (threshold above 3.1e8 in scaled units) only the float32 estimate
+// is left, which is off by one far from any tie: launch_p1_fwd_wave keeps such input -- and it is reachable: 48 / 64 bit depths,
+// unscaled big-endian integers -- away from this kernel (p1_wave_in_range, frad_p1_wave.hip).  The same rule keeps every band's
+// RMS at or below 2^31, the last at which k7_pow04's float32 reciprocal of y^5 ~ rms^4 is a normal number (see there).
 __device__ __forceinline__ int32_t k7_band_code(double t, const double* tqh) {
     if (!(t > 1.0)) return 0;
     const float v = k7_log2f((float)t) * 2.2585796f;          // ln 2 / ln(e / 2)

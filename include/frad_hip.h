@@ -135,7 +135,16 @@ int frad_p4_digital(const void* payload, int64_t payload_stride, int64_t n_frame
  *   q   int32 [n_frames, N, C]  bin-major / channel-minor   (freqs_flat, profile1.py:34-36)
  *   tq  int32 [n_frames, 27, C] band-major / channel-minor  (thres_flat, profile1.py:38-40)
  * The Exp-Golomb-Rice stage that follows (profile1.py:43-45) is frad_p1_golomb_encode below; zlib's deflate
- * (profile1.py:50) stays on the host.                                                                  */
+ * (profile1.py:50) stays on the host.
+ *
+ * Parity (integer and f64 PCM): q and tq are the reference's integers exactly -- asserted over the depths 8 .. 64, the table
+ * rates, loss levels 0.125 .. 50 and either setting of FRAD_RAW_BE_INTS.  The one deviation: the transform is not pocketfft's
+ * (the two agree to 8 eps log2(N) max|X|), so where the reference's own rounding is undecided within that bound -- a value that
+ * close to a half-integer -- either neighbour may be written.  f32 / f16 PCM (the reference's float32 path): |dq| <= 1 on at
+ * most 2 % of the values.
+ * The N = 2048, C <= 2 wave kernel decides in float32 and takes only integer PCM whose type and depth bound the scaled
+ * coefficients by peak <= 2^31 (its thresholds use a float32 reciprocal of rms^4) with peak^0.8 x loss inside the 256-entry
+ * band-code table; f64 PCM, deeper depths and louder unscaled big-endian integers run through the float64 one-shot kernel. */
 int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32_t N, int32_t C,
                      int64_t frame_stride, int32_t n_valid, int32_t bits, int32_t srate, double loss_level,
                      uint32_t flags, int32_t* q, int32_t* tq, void* stream);
@@ -216,8 +225,8 @@ int frad_p2_synth(const int32_t* q, const int32_t* tq, const int32_t* lpc, int64
  * exactly the layout frad_p2_golomb_decode writes, so the three arrays go to frad_p2_synth as they are.  The DCT is profile 0's
  * (frad_p0_analogue at 64-bit little-endian storage, into stream-ordered scratch of n_frames*N*C*8 bytes); the masking, the
  * TNS analysis and the quantiser run in k_p2_analysis, one block per (frame, channel).
- * Parity: the thresholds and the LPC integers are the reference's, the quantised coefficients profile 1's contract (|dq| <= 1
- * on a small fraction of values: the transform is not pocketfft's).  Deviations, all in the last bits of quantities that are
+ * Parity: the thresholds and the LPC integers are the reference's, the quantised coefficients within |dq| <= 1
+ * on a small fraction of values (the transform is not pocketfft's).  Deviations, all in the last bits of quantities that are
  * only compared or rounded: the band energies, the means of lpc_cond / calc_autocorr / predgain and the autocorrelation are
  * block sums, not numpy's pairwise sums or np.correlate's BLAS dot products; a frame whose statistic lands within a few ulps of
  * one of tns_analysis's thresholds (1e-10, 0.5, 0.01, 1e6, MIN_PRED) or an LPC value within an ulp of a rounding boundary can

@@ -342,17 +342,22 @@ def p1_analogue_pre(pcm: np.ndarray, bits: int, srate: int, loss_level: float):
     loss_level = max(abs(loss_level), 0.125)
     channels = pcm.shape[1]
     freqs = dct_channels(pcm)
-    masked, thres = [], []
+    masked, thres, divs = [], [], []
     for c in range(channels):
         t = mask_thresholds(freqs[c] * scale, srate, loss_level)
         div = spread_thresholds(t, dlen, srate)
         div = np.where(div == 0, np.inf, div)
         masked.append(freqs[c] / div)
         thres.append(t)
+        divs.append(div)
     masked, thres = np.array(masked), np.array(thres)
-    q = quant(masked * scale).round().astype(int).T.ravel()
-    tq = dequant(np.log(thres.clip(min=1.0)) / np.log(np.e / 2)).round().astype(int).T.ravel()
-    return q, tq, {"freqs": freqs, "thres": thres, "bits": bits, "srate": srate, "dlen": dlen}
+    y = quant(masked * scale)
+    v = dequant(np.log(thres.clip(min=1.0)) / np.log(np.e / 2))
+    q = y.round().astype(int).T.ravel()
+    tq = v.round().astype(int).T.ravel()
+    # "y" / "v": q and tq before .round(), in their order; "div": the per-bin divisor [C, dlen] (inf where the ramp is 0)
+    return q, tq, {"freqs": freqs, "thres": thres, "bits": bits, "srate": srate, "dlen": dlen, "loss": loss_level,
+                   "y": y.T.ravel(), "v": v.T.ravel(), "div": np.array(divs)}
 
 
 def golomb_encode(data: np.ndarray) -> bytes:

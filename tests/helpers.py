@@ -94,12 +94,15 @@ class EmuBackend:
         return int(flag[0])
 
     # ---- profile 1 ----
-    def p1_analogue(self, raw, fmt, F, N, C, bits, srate, loss, frame_stride=None, n_valid=None):
+    def p1_analogue(self, raw, fmt, F, N, C, bits, srate, loss, frame_stride=None, n_valid=None, raw_be=True, offset=0):
+        """``raw_be``: FRAD_RAW_BE_INTS (the reference's quirk, the encoder's default); ``offset`` (bytes) mis-aligns the PCM"""
         from frad_python_amd.backend.pcmformat import pcm_dtype_code
-        src = np.zeros(raw.nbytes + 64, np.uint8); src[:raw.nbytes] = raw.view(np.uint8).reshape(-1)
+        src = np.zeros(raw.nbytes + offset + 80, np.uint8)
+        base = (-src.ctypes.data) % 16 + offset                # a 16-byte aligned start, then the offset
+        src[base:base + raw.nbytes] = raw.view(np.uint8).reshape(-1)
         q = np.zeros((max(F, 1), N, C), np.int32); tq = np.zeros((max(F, 1), 27, C), np.int32)
-        self.lib.p1_analogue(src.ctypes.data, pcm_dtype_code(fmt), F, N, C, N if frame_stride is None else frame_stride,
-                             N if n_valid is None else n_valid, bits, srate, loss, 2, q.ctypes.data, tq.ctypes.data)
+        self.lib.p1_analogue(src.ctypes.data + base, pcm_dtype_code(fmt), F, N, C, N if frame_stride is None else frame_stride,
+                             N if n_valid is None else n_valid, bits, srate, loss, 2 if raw_be else 0, q.ctypes.data, tq.ctypes.data)
         return q[:F], tq[:F]
 
     def p1_digital(self, q, tq, N, C, bits, srate):
@@ -261,12 +264,13 @@ class GpuBackend:
         return int(flag.item())
 
     # ---- profile 1 ----
-    def p1_analogue(self, raw, fmt, F, N, C, bits, srate, loss, frame_stride=None, n_valid=None):
+    def p1_analogue(self, raw, fmt, F, N, C, bits, srate, loss, frame_stride=None, n_valid=None, raw_be=True, offset=0):
         from frad_python_amd import core
         t = self.torch
-        src = t.zeros(raw.nbytes + 64, dtype=t.uint8, device=self.dev)
-        src[:raw.nbytes] = t.from_numpy(raw.view(np.uint8).reshape(-1).copy()).to(self.dev)
-        q, tq = core.p1_analogue_batch(src, fmt, F, N, C, bits, srate, loss, frame_stride=frame_stride, n_valid=n_valid)
+        src = t.zeros(raw.nbytes + offset + 64, dtype=t.uint8, device=self.dev)
+        src[offset:offset + raw.nbytes] = t.from_numpy(raw.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        q, tq = core.p1_analogue_batch(src[offset:], fmt, F, N, C, bits, srate, loss, frame_stride=frame_stride, n_valid=n_valid,
+                                       raw_be_ints=raw_be)
         t.cuda.synchronize()
         return q.cpu().numpy(), tq.cpu().numpy()
 

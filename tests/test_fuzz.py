@@ -86,23 +86,24 @@ def test_random_geometries_against_oracle():
 def test_random_profile1_geometries_against_oracle():
     """Profile 1 (K7 / K8) over random legal compact frame sizes, rates, depths, loss levels and channel counts."""
     from frad_python_amd.fourier import profiles
-    from test_parity_p1 import _check_ints
+    from test_p1_exact import check_case, frames_of
     be = GpuBackend()
     rng = np.random.default_rng(int(os.environ.get("FRAD_FUZZ_SEED", "20261004")) + 1)
     rounds = int(os.environ.get("FRAD_FUZZ_N", "220")) // 4
     sizes = list(profiles.compact.SAMPLES)                  # every legal compact frame size (profiles.py:14-23), up to 28 672
-    dt = fo.pcm_dtype("s16le")
+    fmts = ["s16le", "u8", "s8", "u16le", "u16be", "s16be", "s32le", "s32be", "u32le", "u32be", "s64le", "s64be", "u64be", "f64le", "f64be"]
     ok = 0
     for _ in range(rounds):
         N = int(rng.choice(sizes)); C = int(rng.choice([1, 2, 2, 3, 6])); F = int(rng.choice([1, 2, 5]))
-        srate = int(rng.choice(profiles.compact.SRATES)); bits = int(rng.choice([8, 12, 16, 24, 32]))
+        srate = int(rng.choice(profiles.compact.SRATES)); bits = int(rng.choice(fo.P1_DEPTHS))
         loss = float(1.25 ** int(rng.integers(0, 21)) / 19.0 + 0.5)
-        raw = synth.to_pcm(synth.harmonic_mix(F * N, C, srate, seed=int(rng.integers(0, 1 << 30))) * rng.uniform(0.05, 1.0), "s16le")
-        q, tq = be.p1_analogue(raw, "s16le", F, N, C, bits, srate, loss)        # every legal geometry runs (refused == 0)
+        fmt = str(rng.choice(fmts))
+        raw = synth.to_pcm(synth.harmonic_mix(F * N, C, srate, seed=int(rng.integers(0, 1 << 30))) * rng.uniform(0.05, 1.0), fmt)
+        q, tq = be.p1_analogue(raw, fmt, F, N, C, bits, srate, loss)            # every legal geometry runs (refused == 0)
+        want = [fo.p1_analogue_pre(frame, bits, srate, loss) for frame in frames_of(raw, fmt, F, N, C)]
+        check_case([(q[f], tq[f]) + want[f] for f in range(F)], f"{(N, C, F, srate, bits, fmt, loss)}")
         for f in range(F):
-            wq, wt, aux = fo.p1_analogue_pre(fo.to_f64(raw[f * N:(f + 1) * N], dt), bits, srate, loss)
-            _check_ints(q[f].reshape(-1), wq, f"q {(N, C, srate, bits, loss, f)}")
-            _check_ints(tq[f].reshape(-1), wt, f"tq {(N, C, srate, bits, loss, f)}")
+            wq, wt, aux = want[f]
             dec = be.p1_digital(wq.reshape(1, N, C).astype(np.int32), wt.reshape(1, 27, C).astype(np.int32), N, C, bits, srate)[0]
             ref = fo.p1_digital_post(wq, wt, fo.P1_DEPTHS.index(bits), C, srate, N)
             assert np.max(np.abs(dec - ref)) <= 1e-12 * max(1.0, np.max(np.abs(ref))), (N, C, srate, bits, loss, f)

@@ -154,6 +154,40 @@ def test_streams_encode_byte_for_byte_and_decode(kind):
             assert np.max(np.abs(got - want)) <= 1e-12 * max(1.0, np.max(np.abs(want))), c["name"]
 
 
+@pytest.mark.parametrize("kind", ["host", pytest.param("gpu", marks=pytest.mark.gpu)])
+@pytest.mark.parametrize("bits,fmt", [(64, "s16le"), (16, "s32be")])
+def test_p1_streams_louder_than_the_wave_kernels_tables(kind, bits, fmt):
+    """Encoder(1, 48000, 2, bits, 2048, fmt) on its default path, 3 frames and a flush tail: at 64 bit, and with big-endian
+    integers (which the reference does not normalise), band codes and coefficients leave the range the N = 2048 wave kernel's
+    float32 decisions hold -- byte-identical to the reference stream all the same."""
+    from test_p1_exact import check_case
+    N, C, tail = 2048, 2, 700
+    raw = synth.to_pcm(synth.harmonic_mix(3 * N + tail, C, 48000, seed=7), fmt)
+    pcm = raw.tobytes()
+    p = dict(profile=1, srate=48000, channels=C, bits=bits, frame_size=N, pcm_format=fmt)
+    out, samples = _encode(kind, pcm, 4096, p)
+    ref = fo.encode_stream(pcm, **p)
+    assert samples == 3 * N + tail
+    if kind == "gpu" and out != ref:
+        # the bytes may differ only where the exact comparator excuses a value: the oracle's own rounding undecided within the
+        # transform bound.  Then compare what the streams hold, frame by frame, under that comparator.
+        fa, fb = _p1_frames(out), _p1_frames(ref)
+        assert len(fa) == len(fb) == 4
+        items = []
+        for i, ((ha, tqa, qa), (hb, _, _)) in enumerate(zip(fa, fb)):
+            assert ha == hb, i
+            frame = fo.to_f64(raw[i * N:(i + 1) * N], fo.pcm_dtype(fmt))
+            wq, wt, aux = fo.p1_analogue_pre(frame, bits, 48000, 0.5)
+            assert len(qa) <= wq.size and len(tqa) <= wt.size, i
+            qa, tqa = np.pad(qa, (0, wq.size - len(qa))), np.pad(tqa, (0, wt.size - len(tqa)))     # the coder drops trailing zeros
+            items.append((qa, tqa, wq, wt, aux))
+        excused = check_case(items, f"stream {fmt} bits {bits}")
+        print(f"[p1 gpu stream] {fmt} bits {bits}: bytes differ from the reference's, {excused} values excused by the comparator")
+        assert excused > 0, "the stream differs from the reference's though no value was excused"
+    else:
+        assert out == ref
+
+
 def test_encoder_rejects_like_the_reference(kind):
     # bits = 0 (the CLI default) fails verify_bit_depth: the reference's constructor ignores the error string
     # and the encoder then silently emits nothing (encoder.py:33, 57-58, 139-140)
