@@ -16,59 +16,61 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfrad_hip.so")
 FRAD_LITTLE_ENDIAN = 1
 FRAD_RAW_BE_INTS = 2
 
-# every symbol include/frad_hip.h declares: name -> (restype, argtypes)
+# every symbol include/frad_hip.h declares: name -> (restype, argtypes).  STATUS is an `int` that is a frad_status: the binding
+# raises FradError unless it is 0; a plain c_int (frad_abi_version, frad_has_fast_path, frad_last_hip_error) is a value.
+STATUS = "frad_status"
 SYMBOLS = {
     "frad_abi_version": (c_int, []),
     "frad_strerror": (c_char_p, [c_int]),
     "frad_last_hip_error": (c_int, []),
     "frad_payload_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "frad_has_fast_path": (c_int, [c_int32, c_int32, c_int32]),
-    "frad_plan_prepare": (c_int, [c_int32, c_int32]),
+    "frad_plan_prepare": (STATUS, [c_int32, c_int32]),
     "frad_plan_clear": (None, []),
-    "frad_p0_analogue": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
+    "frad_p0_analogue": (STATUS, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_p0_analogue_checked": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
+    "frad_p0_analogue_checked": (STATUS, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
                                          c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "frad_p0_overflow_scan": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
-    "frad_p0_digital": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
-    "frad_p0_analogue_clips": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint32,
+    "frad_p0_overflow_scan": (STATUS, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "frad_p0_digital": (STATUS, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
+    "frad_p0_analogue_clips": (STATUS, [c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint32,
                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "frad_p0_digital_clips": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_int64, c_void_p]),
-    "frad_p4_analogue": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
+    "frad_p0_digital_clips": (STATUS, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_int64, c_void_p]),
+    "frad_p4_analogue": (STATUS, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_uint32,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_p4_digital": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
-    "frad_p1_analogue": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32,
+    "frad_p4_digital": (STATUS, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
+    "frad_p1_analogue": (STATUS, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32,
                                  c_double, c_uint32, c_void_p, c_void_p, c_void_p]),
-    "frad_p1_digital": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "frad_crc32_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "frad_p1_overlap_add": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "frad_p1_overlap_add_pcm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_void_p]),
-    "frad_clips_overlap_add": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+    "frad_p1_digital": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_crc32_frames": (STATUS, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "frad_p1_overlap_add": (STATUS, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p1_overlap_add_pcm": (STATUS, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "frad_clips_overlap_add": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
     "frad_p1_golomb_bound": (c_size_t, [c_int32, c_int32]),
-    "frad_p1_golomb_encode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_rows_compact": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "frad_p1_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "frad_p2_golomb_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "frad_p2_synth": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "frad_p2_analogue": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_double, c_uint32,
+    "frad_p1_golomb_encode": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frad_rows_compact": (STATUS, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "frad_p1_golomb_decode": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p2_golomb_decode": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "frad_p2_synth": (STATUS, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_p2_analogue": (STATUS, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_double, c_uint32,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "frad_p2_golomb_bound": (c_size_t, [c_int32, c_int32]),
-    "frad_p2_golomb_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_from_f64": (c_int, [c_void_p, c_int64, c_int32, c_uint32, c_void_p, c_void_p]),
-    "frad_p0_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
-    "frad_p4_digital_pcm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
-    "frad_p1_digital_pcm": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
+    "frad_p2_golomb_encode": (STATUS, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frad_from_f64": (STATUS, [c_void_p, c_int64, c_int32, c_uint32, c_void_p, c_void_p]),
+    "frad_p0_digital_pcm": (STATUS, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
+    "frad_p4_digital_pcm": (STATUS, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_uint32, c_int32, c_void_p, c_void_p]),
+    "frad_p1_digital_pcm": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
     "frad_asfh_scan": (c_int64, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_rs_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
-    "frad_rs_repair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+    "frad_rs_encode": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_rs_repair": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
-    "frad_rs_encode_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
-    "frad_crc16_ansi_frames": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "frad_inflate_raw": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "frad_deflate_raw": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "frad_rs_encode_frames": (STATUS, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "frad_crc16_ansi_frames": (STATUS, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "frad_inflate_raw": (STATUS, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "frad_deflate_raw": (STATUS, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "frad_deflate_stride": (c_int64, [c_int64]),
-    "frad_bench_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "frad_bench_copy": (STATUS, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 
@@ -92,7 +94,12 @@ class FradError(RuntimeError):
 
 
 class FradLib:
-    """One loaded copy of the C-ABI library; methods take raw pointers (ints) and sizes."""
+    """One loaded copy of the C-ABI library; methods take raw pointers (ints) and sizes.
+
+    Every symbol of ``SYMBOLS`` is a method named like the symbol without ``frad_``, with the C parameters in the C order,
+    generated in ``__init__``: a status entry point raises ``FradError`` unless it returns 0, and its trailing ``stream`` may
+    be left out (NULL, the default stream); any other entry point returns its value.  The methods written out below are the
+    ones whose Python signature is deliberately not the C one."""
 
     def __init__(self, path: str = LIB_PATH):
         if not os.path.exists(path):
@@ -111,12 +118,24 @@ class FradLib:
         self.dll = ctypes.CDLL(path)
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(self.dll, name)           # AttributeError if the library lacks a symbol
-            fn.restype, fn.argtypes = res, args
+            fn.restype, fn.argtypes = (c_int if res is STATUS else res), args
+            if not hasattr(FradLib, name[5:]):     # (a method written out below keeps its own signature)
+                setattr(self, name[5:], self._checked(fn, len(args)) if res is STATUS else fn)
+
+    def _checked(self, fn, n_args: int):
+        """the method of a status entry point; ``stream``, its last parameter, defaults to 0"""
+        def call(*args):
+            rc = fn(*args) if len(args) == n_args else fn(*args, 0)
+            if rc:
+                self._check(rc)
+        call.__name__ = fn.__name__[5:]
+        return call
 
     def _check(self, rc: int):
         if rc != 0:
             raise FradError(rc, self.dll.frad_strerror(rc).decode(), self.dll.frad_last_hip_error())
 
+    # casts and defaults
     def payload_bytes(self, N, C, bits):
         return int(self.dll.frad_payload_bytes(N, C, bits))
 
@@ -126,83 +145,26 @@ class FradLib:
     def plan_prepare(self, N, f32=False):
         self._check(self.dll.frad_plan_prepare(N, int(f32)))
 
-    def p0_analogue(self, pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload, payload_stride, absmax, stream=0):
-        self._check(self.dll.frad_p0_analogue(pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload,
-                                               payload_stride, absmax, stream))
+    def deflate_stride(self, max_body_bytes):
+        """a negative result is a frad_status"""
+        r = int(self.dll.frad_deflate_stride(max_body_bytes))
+        self._check(r if r < 0 else 0)
+        return r
 
-    def p0_analogue_checked(self, pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload, payload_stride, absmax, flag, stream=0):
-        self._check(self.dll.frad_p0_analogue_checked(pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload,
-                                                       payload_stride, absmax, flag, stream))
-
-    def crc32_frames(self, data, stride, n_frames, nbytes, out, stream=0):
-        self._check(self.dll.frad_crc32_frames(data, stride, n_frames, nbytes, out, stream))
-
-    def p0_overflow_scan(self, absmax, n_frames, bits, flag, stream=0):
-        self._check(self.dll.frad_p0_overflow_scan(absmax, n_frames, bits, flag, stream))
-
-    def p0_digital(self, payload, payload_stride, n_frames, N, C, bits, flags, out, stream=0):
-        self._check(self.dll.frad_p0_digital(payload, payload_stride, n_frames, N, C, bits, flags, out, stream))
-
-    def p0_analogue_clips(self, pcm, dtype, n_clips, clip_stride, frames_per_clip, N, C, bits, flags, payload, payload_stride, absmax, flag, stream=0):
-        self._check(self.dll.frad_p0_analogue_clips(pcm, dtype, n_clips, clip_stride, frames_per_clip, N, C, bits, flags, payload,
-                                                     payload_stride, absmax, flag, stream))
-
-    def p0_digital_clips(self, payload, payload_stride, n_clips, frames_per_clip, N, C, bits, flags, out, out_clip_stride, stream=0):
-        self._check(self.dll.frad_p0_digital_clips(payload, payload_stride, n_clips, frames_per_clip, N, C, bits, flags, out, out_clip_stride, stream))
-
-    def p4_analogue(self, pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload, payload_stride, absmax, stream=0):
-        self._check(self.dll.frad_p4_analogue(pcm, dtype, n_frames, N, C, frame_stride, bits, flags, payload,
-                                               payload_stride, absmax, stream))
-
-    def p4_digital(self, payload, payload_stride, n_frames, N, C, bits, flags, out, stream=0):
-        self._check(self.dll.frad_p4_digital(payload, payload_stride, n_frames, N, C, bits, flags, out, stream))
-
-    def p1_analogue(self, pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate, loss_level, flags, q, tq, stream=0):
-        self._check(self.dll.frad_p1_analogue(pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate,
-                                               loss_level, flags, q, tq, stream))
-
-    def p1_digital(self, q, tq, n_frames, N, C, bits, srate, out, stream=0):
-        self._check(self.dll.frad_p1_digital(q, tq, n_frames, N, C, bits, srate, out, stream))
-
-    def p1_golomb_bound(self, N, C):
-        return int(self.dll.frad_p1_golomb_bound(N, C))
-
-    def p1_golomb_encode(self, q, tq, n_frames, N, C, bodies, body_stride, body_bytes, stream=0):
-        self._check(self.dll.frad_p1_golomb_encode(q, tq, n_frames, N, C, bodies, body_stride, body_bytes, stream))
-
-    def rows_compact(self, rows, row_stride, row_bytes, n_rows, out, offsets, stream=0):
-        self._check(self.dll.frad_rows_compact(rows, row_stride, row_bytes, n_rows, out, offsets, stream))
-
-    def p1_golomb_decode(self, bodies, offsets, n_frames, N, C, q, tq, status, stream=0):
-        self._check(self.dll.frad_p1_golomb_decode(bodies, offsets, n_frames, N, C, q, tq, status, stream))
-
-    def p2_golomb_decode(self, bodies, offsets, n_frames, N, C, q, tq, lpc, status, stream=0):
-        self._check(self.dll.frad_p2_golomb_decode(bodies, offsets, n_frames, N, C, q, tq, lpc, status, stream))
-
-    def p2_synth(self, q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream=0):
-        self._check(self.dll.frad_p2_synth(q, tq, lpc, n_frames, N, C, bits, srate, coeffs_out, stream))
-
-    def p2_analogue(self, pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate, loss_level, flags, q, tq, lpc, stream=0):
-        self._check(self.dll.frad_p2_analogue(pcm, dtype, n_frames, N, C, frame_stride, n_valid, bits, srate, loss_level, flags,
-                                              q, tq, lpc, stream))
-
-    def p2_golomb_bound(self, N, C):
-        return int(self.dll.frad_p2_golomb_bound(N, C))
-
-    def p2_golomb_encode(self, q, tq, lpc, n_frames, N, C, bodies, body_stride, body_bytes, stream=0):
-        self._check(self.dll.frad_p2_golomb_encode(q, tq, lpc, n_frames, N, C, bodies, body_stride, body_bytes, stream))
-
+    # `flags` sits behind the stream and defaults to FRAD_RAW_BE_INTS: these four take the reference's from_f64 as it is
     def from_f64(self, pcm, n_values, out_dtype, out, stream=0, flags=FRAD_RAW_BE_INTS):
         self._check(self.dll.frad_from_f64(pcm, n_values, out_dtype, flags, out, stream))
 
-    def p0_digital_pcm(self, payload, payload_stride, n_frames, N, C, bits, flags, out_dtype, out, stream=0):
-        self._check(self.dll.frad_p0_digital_pcm(payload, payload_stride, n_frames, N, C, bits, flags, out_dtype, out, stream))
-
-    def p4_digital_pcm(self, payload, payload_stride, n_frames, N, C, bits, flags, out_dtype, out, stream=0):
-        self._check(self.dll.frad_p4_digital_pcm(payload, payload_stride, n_frames, N, C, bits, flags, out_dtype, out, stream))
-
     def p1_digital_pcm(self, q, tq, n_frames, N, C, bits, srate, out_dtype, out, stream=0, flags=FRAD_RAW_BE_INTS):
         self._check(self.dll.frad_p1_digital_pcm(q, tq, n_frames, N, C, bits, srate, out_dtype, flags, out, stream))
+
+    def p1_overlap_add_pcm(self, frames, n_frames, N, C, ratio, prev_tail, out_dtype, out, next_tail, stream=0, flags=FRAD_RAW_BE_INTS):
+        self._check(self.dll.frad_p1_overlap_add_pcm(frames, n_frames, N, C, ratio, prev_tail, out_dtype, flags, out, next_tail, stream))
+
+    def clips_overlap_add(self, frames, clip_frame0, n_clips, N, C, ratio, tails, tail_off, tail_rows, tail_win, out_dtype, out, out_off,
+                          out_rows, stream=0, flags=FRAD_RAW_BE_INTS):
+        self._check(self.dll.frad_clips_overlap_add(frames, clip_frame0, n_clips, N, C, ratio, tails, tail_off, tail_rows, tail_win,
+                                                    out_dtype, flags, out, out_off, out_rows, stream))
 
     def asfh_scan(self, data, start: int = 0, max_frames: int = 0):
         """frad_asfh_scan over a bytes-like object -> (numpy structured table, next_pos, stop_reason)"""
@@ -220,44 +182,6 @@ class FradLib:
         if rows < 0:
             self._check(int(rows))
         return table[:rows], int(nxt.value), int(why.value)
-
-    def rs_encode(self, data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, stream=0):
-        self._check(self.dll.frad_rs_encode(data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, stream))
-
-    def rs_repair(self, data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected, failed, work, stream=0):
-        self._check(self.dll.frad_rs_repair(data, in_off, blk_off, out_off, n_frames, n_blocks, dsize, codesize, out, corrected,
-                                            failed, work, stream))
-
-    def rs_encode_frames(self, data, in_stride, n_frames, nbytes, dsize, codesize, out, out_stride, stream=0):
-        self._check(self.dll.frad_rs_encode_frames(data, in_stride, n_frames, nbytes, dsize, codesize, out, out_stride, stream))
-
-    def crc16_ansi_frames(self, data, offsets, n_frames, out, stream=0):
-        self._check(self.dll.frad_crc16_ansi_frames(data, offsets, n_frames, out, stream))
-
-    def inflate_raw(self, src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream=0):
-        self._check(self.dll.frad_inflate_raw(src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream))
-
-    def deflate_raw(self, src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream=0):
-        self._check(self.dll.frad_deflate_raw(src, src_offsets, n_frames, dst, dst_stride, dst_bytes, status, stream))
-
-    def deflate_stride(self, max_body_bytes):
-        r = int(self.dll.frad_deflate_stride(max_body_bytes))
-        self._check(r if r < 0 else 0)
-        return r
-
-    def bench_copy(self, src, dst, nbytes, stream=0):
-        self._check(self.dll.frad_bench_copy(src, dst, nbytes, stream))
-
-    def p1_overlap_add_pcm(self, frames, n_frames, N, C, ratio, prev_tail, out_dtype, out, next_tail, stream=0, flags=FRAD_RAW_BE_INTS):
-        self._check(self.dll.frad_p1_overlap_add_pcm(frames, n_frames, N, C, ratio, prev_tail, out_dtype, flags, out, next_tail, stream))
-
-    def clips_overlap_add(self, frames, clip_frame0, n_clips, N, C, ratio, tails, tail_off, tail_rows, tail_win, out_dtype, out, out_off,
-                          out_rows, stream=0, flags=FRAD_RAW_BE_INTS):
-        self._check(self.dll.frad_clips_overlap_add(frames, clip_frame0, n_clips, N, C, ratio, tails, tail_off, tail_rows, tail_win,
-                                                    out_dtype, flags, out, out_off, out_rows, stream))
-
-    def p1_overlap_add(self, frames, n_frames, N, C, ratio, prev_tail, out, next_tail, stream=0):
-        self._check(self.dll.frad_p1_overlap_add(frames, n_frames, N, C, ratio, prev_tail, out, next_tail, stream))
 
 
 _lib: FradLib | None = None

@@ -21,6 +21,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import ecc
+from .backend.pcmformat import ff_format_to_numpy_type
+from .frames import raw_deflate
+
 
 class HipBridge:
     _pinned = None
@@ -81,7 +85,7 @@ class HipBridge:
         t, core = self.torch, self.core
         if bits not in core.DEPTHS:
             bits = 16
-        nb = core._lib.load().payload_bytes(N, C, bits)
+        nb = core.payload_bytes(N, C, bits)
         plen = nb if ecc_ratio is None else core.rs_protected_bytes(nb, *ecc_ratio)
         if n_frames == 0 or plen >= 0xFFFFFFFF:
             return None
@@ -107,23 +111,20 @@ class HipBridge:
         t.cuda.current_stream(self.device).synchronize()
         return host.numpy().view(dtype).reshape(shape)
 
+    def _down_pcm(self, dev, out_format, shape) -> np.ndarray:
+        """``_down_array`` of samples the device narrowed to ``out_format``, or of float64 ones without"""
+        return self._down_array(dev, np.float64 if out_format is None else ff_format_to_numpy_type(out_format), shape)
+
     def lossless_decode_strided(self, profile, region, n_frames, stride, nbytes, N, C, bits, little_endian, out_format=None) -> np.ndarray:
         """Frames that sit equally spaced in the stream (``region`` = first payload byte .. last payload byte, a
         read-only buffer): one H2D copy of the region, headers and all, and the kernels step over it with
         ``payload_stride = stride``; no per-frame host copies."""
-        import warnings
-        t = self.torch
-        if nbytes != self.core._lib.load().payload_bytes(N, C, bits):
+        if nbytes != self.core.payload_bytes(N, C, bits):
             return None                                       # header length and geometry disagree: frame-by-frame path decides
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")                   # read-only buffer: it is only copied to the device
-            dev = t.frombuffer(region, dtype=t.uint8).to(self.device)
-        if out_format is not None:                            # narrowed on the device: 2-4x fewer bytes over PCIe
-            from .backend.pcmformat import ff_format_to_numpy_type
-            out = self.core.digital_batch(profile, dev, n_frames, N, C, bits, little_endian, payload_stride=stride, out_format=out_format)
-            return self._down_array(out, ff_format_to_numpy_type(out_format), (n_frames, N, C))
-        out = self.core.digital_batch(profile, dev, n_frames, N, C, bits, little_endian, payload_stride=stride)
-        return self._down_array(out, np.float64, (n_frames, N, C))
+        # with out_format the samples are narrowed on the device: 2-4x fewer bytes over PCIe
+        out = self.core.digital_batch(profile, self._up(region), n_frames, N, C, bits, little_endian, payload_stride=stride,
+                                      out_format=out_format)
+        return self._down_pcm(out, out_format, (n_frames, N, C))
 
     def lossless_decode(self, profile, payloads: list, N, C, bits, little_endian, keep=False):
         """equally long profile-0 / 4 payloads -> float64 frames [n, N, C]: one upload, one launch, one download; with
@@ -176,24 +177,19 @@ class HipBridge:
         ``zlib.compressobj(-1, DEFLATED, -15)`` of each body (profile1.py:50, profile2.py:54): frad_deflate_raw, the rows
         compacted with frad_rows_compact, one copy back of the payloads with their offsets and statuses.  A body the device
         leaves to the host (status 1: 65 274 bytes or more) is copied back alone and deflated by zlib."""
-        import zlib
         t, core = self.torch, self.core
-        lib = core._lib.load()
         n = offsets.numel() - 1
         if n == 0:
             return []
         rows, nbytes, status = core.deflate_batch(flat, offsets)
-        stride = rows.shape[1]
-        pay_off = t.empty(n + 1, dtype=t.int64, device=self.device)
-        with t.cuda.device(self.device):
-            lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, 0, pay_off.data_ptr(), core._stream_ptr())
-            total = int(pay_off[-1].item())
-            head = (total + 7) // 8 * 8
-            out = t.empty(head + 8 * (n + 1) + 4 * n, dtype=t.uint8, device=self.device)    # payloads | offsets | statuses
-            if total:
-                lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, out.data_ptr(), pay_off.data_ptr(), core._stream_ptr())
-            out[head:head + 8 * (n + 1)].view(t.int64).copy_(pay_off)
-            out[head + 8 * (n + 1):].view(t.int32).copy_(status)
+        pay_off = core.rows_offsets(rows, nbytes)
+        total = int(pay_off[-1].item())                                   # the one host read: the size of the result
+        head = (total + 7) // 8 * 8
+        out = t.empty(head + 8 * (n + 1) + 4 * n, dtype=t.uint8, device=self.device)        # payloads | offsets | statuses
+        if total:
+            core.rows_gather(rows, nbytes, pay_off, out)
+        out[head:head + 8 * (n + 1)].view(t.int64).copy_(pay_off)
+        out[head + 8 * (n + 1):].view(t.int32).copy_(status)
         host = self._down_bytes(out)
         off = np.frombuffer(host, np.int64, n + 1, head)
         st = np.frombuffer(host, np.int32, n, head + 8 * (n + 1))
@@ -203,8 +199,7 @@ class HipBridge:
             boff = offsets.cpu().numpy()
             for i in left.tolist():
                 body = self._down_bytes(flat[int(boff[i]):int(boff[i + 1])]) if boff[i + 1] > boff[i] else b""
-                co = zlib.compressobj(zlib.Z_DEFAULT_COMPRESSION, zlib.DEFLATED, -15)
-                pays[i] = co.compress(body) + co.flush()
+                pays[i] = raw_deflate(body)
         self.last_deflate_host = int(left.size)
         return pays
 
@@ -215,22 +210,18 @@ class HipBridge:
         (status != 0): the caller then takes the whole run through the host's zlib.  One upload of the payloads, one
         download of two numbers."""
         t, core = self.torch, self.core
-        lib = core._lib.load()
-        n = len(payloads)
-        off = np.zeros(n + 1, np.int64)
+        off = np.zeros(len(payloads) + 1, np.int64)
         np.cumsum([len(p) for p in payloads], out=off[1:])
         src = self._up(b"".join(payloads))
-        stride = lib.p1_golomb_bound(N, C) if profile == 1 else lib.p2_golomb_bound(N, C)     # multiples of 16
+        stride = core.golomb_bound(profile, N, C)                         # a multiple of 16
         rows, nbytes, status = core.inflate_batch(src, t.from_numpy(off).to(self.device), stride)
-        offsets = t.empty(n + 1, dtype=t.int64, device=self.device)
-        with t.cuda.device(self.device):
-            lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, 0, offsets.data_ptr(), core._stream_ptr())
-            bad, total = t.stack([(status != 0).any().to(t.int64), offsets[-1]]).tolist()
-            if bad:
-                return None
-            bodies = t.zeros(total + 8, dtype=t.uint8, device=self.device)
-            if total:
-                lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, bodies.data_ptr(), offsets.data_ptr(), core._stream_ptr())
+        offsets = core.rows_offsets(rows, nbytes)
+        bad, total = t.stack([(status != 0).any().to(t.int64), offsets[-1]]).tolist()      # the one host read
+        if bad:
+            return None
+        bodies = t.zeros(total + 8, dtype=t.uint8, device=self.device)   # 8 zeroed bytes of slack behind the last body
+        if total:
+            core.rows_gather(rows, nbytes, offsets, bodies)
         return bodies, offsets
 
     # ------------------------------------------------------------------ the compact decode chain: source, frames, sink
@@ -262,7 +253,6 @@ class HipBridge:
         out, nxt = self.core.p1_overlap_add(frames, ratio, pt, out_format=out_format)
         pcm = out.cpu().numpy()
         if out.dtype == t.uint8:
-            from .backend.pcmformat import ff_format_to_numpy_type
             pcm = np.frombuffer(pcm.tobytes(), ff_format_to_numpy_type(out_format))
         return pcm, nxt.cpu().numpy()
 
@@ -300,7 +290,6 @@ class HipBridge:
         device tensor (``keep``) from compact_decode / lossless_decode, or an ndarray, ``tails``: the last-frame tensors, concatenated here in the order
         ``tail_off`` counts them.  -> (out, out_off): a device tensor with ``as_tensor``, else one download into an ndarray
         [rows, C] of float64 or of ``out_format``'s dtype."""
-        from .backend.pcmformat import ff_format_to_numpy_type
         t = self.torch
         dev = lambda a: a if isinstance(a, t.Tensor) else t.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
         frames = dev(frames) if frames is not None else None
@@ -309,10 +298,9 @@ class HipBridge:
         out, out_off = self.core.clips_overlap_add(frames, clip_frame0, N, C, ratio, flat, tail_off, tail_rows, out_format, tail_win)
         if as_tensor:
             return out, out_off
-        if out_format is None:
-            return self._down_array(out, np.float64, (-1, C)) if out.numel() else np.zeros((0, C)), out_off
-        dt = ff_format_to_numpy_type(out_format)
-        return self._down_array(out, dt, (-1, C)) if out.numel() else np.zeros((0, C), dt), out_off
+        if not out.numel():
+            return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
+        return self._down_pcm(out, out_format, (-1, C)), out_off
 
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch
@@ -324,89 +312,73 @@ class HipBridge:
         return self._crossfade(self.torch.from_numpy(np.ascontiguousarray(frames)).to(self.device), ratio, prev_tail)
 
     # ------------------------------------------------------------------ Reed-Solomon (csrc/frad_ecc.hip)
-    def _rs_upload(self, payloads, dsize, codesize, repair):
-        from . import ecc
+    def _rs_launch(self, payloads, dsize, codesize, repair=False, tail=0):
+        """What the three methods below share up to the launch: one upload of ``ecc.pack``'s buffer (the payloads and the
+        three offset arrays), the output buffer -- with ``tail`` bytes behind its 16-byte-aligned data for what the caller
+        sends back in the same download -- and frad_rs_encode or, ``repair``, frad_rs_repair.
+        -> (packed, head, out, out_off, the repair's counters or None)"""
+        t, core = self.torch, self.core
         buf, head, n_blocks, out_off = ecc.pack(payloads, dsize, codesize, repair)
-        dev = self.torch.from_numpy(buf).to(self.device)                  # payloads + the three offset arrays: one H2D copy
-        n1 = len(payloads) + 1
-        p = dev.data_ptr()
-        return dev, (p, p + head, p + head + 8 * n1, p + head + 16 * n1), n_blocks, out_off
+        packed = t.from_numpy(buf).to(self.device)                        # payloads + the three offset arrays: one H2D copy
+        room = (int(out_off[-1]) + 15) // 16 * 16
+        out = t.empty(room + tail if tail else max(room, 16), dtype=t.uint8, device=self.device)
+        launch = core.rs_repair_packed if repair else core.rs_encode_packed
+        return packed, head, out, out_off, launch(packed, head, len(payloads), n_blocks, dsize, codesize, out)
+
+    def _rs_down(self, out, out_off, whole=False):
+        """one download of the outputs (``whole``: of everything behind them too) -> (output i = host[out_off[i]:out_off[i + 1]], host)"""
+        nout = int(out_off[-1])
+        host = self._down_bytes(out if whole else out[:nout]) if whole or nout else b""
+        return [host[out_off[i]:out_off[i + 1]] for i in range(len(out_off) - 1)], host
 
     def rs_encode(self, payloads: list, dsize: int, codesize: int, crc32: bool = False):
         """ecc.encode(p, dsize, codesize) of every payload (tools/ecc.py:6-12): one upload, one launch, one download.
         With ``crc32`` also zlib.crc32 of every protected payload, computed on the device (frad_crc32_frames over each run
         of equally long outputs): -> (outputs, crcs)."""
         t = self.torch
-        lib = self.core._lib.load()
         n = len(payloads)
         if n == 0:
             return ([], []) if crc32 else []
-        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, False)
-        nout = int(out_off[-1])
-        out = t.empty(max((nout + 15) // 16 * 16, 16), dtype=t.uint8, device=self.device)
-        stream = int(t.cuda.current_stream(self.device).cuda_stream)
-        with t.cuda.device(self.device):
-            lib.rs_encode(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), stream)
-            crcs = None
-            if crc32:
-                lens = np.diff(out_off)
-                crc_dev = t.zeros(n, dtype=t.int32, device=self.device)
-                i = 0
-                while i < n:                                              # runs of equal length: one launch each
-                    j = i + 1
-                    while j < n and lens[j] == lens[i]:
-                        j += 1
-                    lib.crc32_frames(out.data_ptr() + int(out_off[i]), int(lens[i]), j - i, int(lens[i]),
-                                     crc_dev.data_ptr() + 4 * i, stream)
-                    i = j
-                crcs = crc_dev.cpu().numpy().view(np.uint32).tolist()
-        host = self._down_bytes(out[:nout]) if nout else b""
-        outs = [host[out_off[i]:out_off[i + 1]] for i in range(n)]
-        del dev
+        _, _, out, out_off, _ = self._rs_launch(payloads, dsize, codesize)
+        crcs = None
+        if crc32:
+            lens = np.diff(out_off)
+            crc_dev = t.zeros(n, dtype=t.int32, device=self.device)
+            i = 0
+            while i < n:                                                  # runs of equal length: one launch each
+                j = i + 1
+                while j < n and lens[j] == lens[i]:
+                    j += 1
+                L = int(lens[i])
+                self.core.crc32_frames(out.as_strided((j - i, L), (L, 1), int(out_off[i])), L, out=crc_dev[i:j])
+                i = j
+            crcs = crc_dev.cpu().numpy().view(np.uint32).tolist()
+        outs, _ = self._rs_down(out, out_off)
         return (outs, crcs) if crc32 else outs
 
     def rs_encode_crc16(self, payloads: list, dsize: int, codesize: int):
         """ecc.encode of every payload and common.crc16_ansi of every protected payload (the compact-profile ECC header's
         checksum), both on the device: one upload, ``frad_rs_encode`` and ``frad_crc16_ansi_frames``, one download of the
         protected bytes with the checksums behind them.  -> (outputs, crcs)"""
-        t, core = self.torch, self.core
-        lib = core._lib.load()
+        t = self.torch
         n = len(payloads)
         if n == 0:
             return [], []
-        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, False)
-        nout = int(out_off[-1])
-        head = (nout + 15) // 16 * 16
-        out = t.empty(head + 2 * n, dtype=t.uint8, device=self.device)          # protected bytes | uint16 checksums
-        n1 = n + 1
-        off_dev = dev[ptrs[3] - ptrs[0]:ptrs[3] - ptrs[0] + 8 * n1].view(t.int64)   # out_off, uploaded with the payloads
-        stream = int(t.cuda.current_stream(self.device).cuda_stream)
-        with t.cuda.device(self.device):
-            lib.rs_encode(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), stream)
-            crc = core.crc16_ansi_frames(out[:nout], off_dev)
-            out[head:].view(t.int16).copy_(crc)
-        host = self._down_bytes(out)
-        crcs = np.frombuffer(host, np.uint16, n, head).tolist()
-        del dev
-        return [host[out_off[i]:out_off[i + 1]] for i in range(n)], crcs
+        packed, head, out, out_off, _ = self._rs_launch(payloads, dsize, codesize, tail=2 * n)    # protected bytes | uint16 checksums
+        o = ecc.pack_layout(head, n)[3]
+        off_dev = packed[o:o + 8 * (n + 1)].view(t.int64)                 # out_off, uploaded with the payloads
+        crc = self.core.crc16_ansi_frames(out[:int(out_off[-1])], off_dev)
+        out[out.numel() - 2 * n:].view(t.int16).copy_(crc)
+        outs, host = self._rs_down(out, out_off, whole=True)
+        return outs, np.frombuffer(host, np.uint16, n, len(host) - 2 * n).tolist()
 
     def rs_repair(self, payloads: list, dsize: int, codesize: int):
         """ecc.decode(p, dsize, codesize, repair=True) of every payload (tools/ecc.py:14-25) on the device.
         -> (data parts, corrected blocks per payload, failed blocks per payload)"""
-        t = self.torch
-        lib = self.core._lib.load()
         n = len(payloads)
         if n == 0:
             return [], np.zeros(0, np.int32), np.zeros(0, np.int32)
-        dev, ptrs, n_blocks, out_off = self._rs_upload(payloads, dsize, codesize, True)
-        nout = int(out_off[-1])
-        out = t.empty(max((nout + 15) // 16 * 16, 16), dtype=t.uint8, device=self.device)
-        counts = t.empty(2 * n + n_blocks + 1, dtype=t.int32, device=self.device)    # corrected, failed, work list
-        stream = int(t.cuda.current_stream(self.device).cuda_stream)
-        with t.cuda.device(self.device):
-            lib.rs_repair(*ptrs, n, n_blocks, dsize, codesize, out.data_ptr(), counts.data_ptr(), counts.data_ptr() + 4 * n,
-                          counts.data_ptr() + 8 * n, stream)
-        host = self._down_bytes(out[:nout]) if nout else b""
-        cnt = counts[:2 * n].cpu().numpy()
-        del dev
-        return [host[out_off[i]:out_off[i + 1]] for i in range(n)], cnt[:n].copy(), cnt[n:].copy()
+        _, _, out, out_off, counts = self._rs_launch(payloads, dsize, codesize, repair=True)
+        outs, _ = self._rs_down(out, out_off)
+        cnt = counts.cpu().numpy()
+        return outs, cnt[:n].copy(), cnt[n:].copy()

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ecc
 from .backend.pcmformat import itemsize_of, pcm_dtype_code
 
 DEPTHS = (12, 16, 24, 32, 48, 64)                      # ref: fourier/profile0.py:4, profile4.py:4
@@ -22,18 +22,12 @@ FLOAT_MAX = {12: 65504.0, 16: 65504.0, 24: float(np.finfo("f4").max), 32: float(
 _ESCALATE = {12: 16, 16: 24, 24: 32, 32: 48, 48: 64, 64: 128}
 
 
-def _require_cuda(t: torch.Tensor, what: str):
+def _require_cuda(t: torch.Tensor, what: str, contiguous: bool = True):
     if not t.is_cuda:
         raise RuntimeError(f"{what} must live in MI355X device memory (got a {t.device} tensor); "
                            "the transform core has no CPU path")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError(f"{what} must be contiguous")
-
-
-def _require_cuda_any(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} must live in MI355X device memory (got a {t.device} tensor); "
-                           "the transform core has no CPU path")
 
 
 def _stream_ptr() -> int:
@@ -42,6 +36,40 @@ def _stream_ptr() -> int:
 
 def _align16(n: int) -> int:
     return (n + 15) // 16 * 16
+
+
+def payload_bytes(N: int, C: int, bits: int) -> int:
+    """bytes of one profile-0 / 4 payload (frad_payload_bytes)"""
+    return _lib.load().payload_bytes(N, C, bits)
+
+
+def _require_pcm_span(pcm: torch.Tensor, n_frames: int, hop: int, n_valid: int, C: int, code: int):
+    """frame i reads ``n_valid`` sample-frames of C elements, ``i * hop`` sample-frames into ``pcm``: the last one must end inside it"""
+    need = ((n_frames - 1) * hop + n_valid) * C * itemsize_of(code) if n_frames else 0
+    if pcm.numel() * pcm.element_size() < need:
+        raise ValueError(f"pcm holds {pcm.numel() * pcm.element_size()} bytes, {need} needed")
+
+
+def _clip_frames(clip_len: int, N: int, first: int, frames_per_clip: int | None) -> int:
+    """frames of N sample-frames per clip from ``first`` on (default: as many whole ones as fit)"""
+    fpc = (clip_len - first) // N if frames_per_clip is None else frames_per_clip
+    if fpc < 1 or first < 0 or first + fpc * N > clip_len:
+        raise ValueError("the frames do not fit the clip")
+    return fpc
+
+
+def _p0_encode_buffers(lib, n_frames: int, N: int, C: int, bits: int, little_endian: bool, raw_be_ints: bool, out, absmax, device):
+    """What the two profile-0 encoders settle before the launch -> (bits, nbytes, flags, out, absmax): the depth default,
+    the flag word, and ``out`` uint8 [n_frames, align16(nbytes)] / ``absmax`` float64 [n_frames] where the caller brought none."""
+    if bits not in DEPTHS:
+        bits = 16                                         # ref: profile0.py:15
+    nbytes = lib.payload_bytes(N, C, bits)
+    if out is None:
+        out = torch.empty((n_frames, _align16(nbytes)), dtype=torch.uint8, device=device)
+    if absmax is None:
+        absmax = torch.empty(n_frames, dtype=torch.float64, device=device)
+    flags = (int(little_endian) * _lib.FRAD_LITTLE_ENDIAN) | (int(raw_be_ints) * _lib.FRAD_RAW_BE_INTS)
+    return bits, nbytes, flags, out, absmax
 
 
 def escalate_depth(absmax: float, bits: int) -> int:
@@ -84,21 +112,11 @@ def analogue_batch(profile: int, pcm: torch.Tensor, pcm_format: str, n_frames: i
     sample-frames after frame i-1.  ``overflow_flag`` (profile 0, device int32 scalar): the batch form of the reference's
     overflow test in the same pass -- set to 1 when a frame needs a deeper format, read it when the answer is needed."""
     _require_cuda(pcm, "pcm")
-    if bits not in DEPTHS:
-        bits = 16                                         # ref: profile0.py:15
     lib = _lib.load()
     code = pcm_dtype_code(pcm_format)
     stride_frames = N if frame_stride is None else frame_stride
-    need = ((n_frames - 1) * stride_frames + N) * C * itemsize_of(code) if n_frames else 0
-    if pcm.numel() * pcm.element_size() < need:
-        raise ValueError(f"pcm holds {pcm.numel() * pcm.element_size()} bytes, {need} needed")
-    nbytes = lib.payload_bytes(N, C, bits)
-    stride = _align16(nbytes)
-    if out is None:
-        out = torch.empty((n_frames, stride), dtype=torch.uint8, device=pcm.device)
-    if absmax is None:
-        absmax = torch.empty(n_frames, dtype=torch.float64, device=pcm.device)
-    flags = (int(little_endian) * _lib.FRAD_LITTLE_ENDIAN) | (int(raw_be_ints) * _lib.FRAD_RAW_BE_INTS)
+    _require_pcm_span(pcm, n_frames, stride_frames, N, C, code)
+    bits, nbytes, flags, out, absmax = _p0_encode_buffers(lib, n_frames, N, C, bits, little_endian, raw_be_ints, out, absmax, pcm.device)
     fn = lib.p4_analogue if profile == 4 else lib.p0_analogue
     with torch.cuda.device(pcm.device):
         if overflow_flag is not None and profile != 4:
@@ -146,23 +164,14 @@ def analogue_clips(clips: torch.Tensor, pcm_format: str, N: int, bits: int, litt
     _require_cuda(clips, "clips")
     if clips.dim() != 3:
         raise ValueError("clips must be [n_clips, clip_len, C]")
-    if bits not in DEPTHS:
-        bits = 16
     lib = _lib.load()
     code = pcm_dtype_code(pcm_format)
     n_clips, clip_len, C = clips.shape
     if clips.element_size() != itemsize_of(code):
         raise ValueError("clips' element size does not match pcm_format")
-    fpc = (clip_len - first) // N if frames_per_clip is None else frames_per_clip
-    if fpc < 1 or first < 0 or first + fpc * N > clip_len:
-        raise ValueError("the frames do not fit the clip")
-    n_frames = n_clips * fpc
-    nbytes = lib.payload_bytes(N, C, bits)
-    if out is None:
-        out = torch.empty((n_frames, _align16(nbytes)), dtype=torch.uint8, device=clips.device)
-    if absmax is None:
-        absmax = torch.empty(n_frames, dtype=torch.float64, device=clips.device)
-    flags = (int(little_endian) * _lib.FRAD_LITTLE_ENDIAN) | (int(raw_be_ints) * _lib.FRAD_RAW_BE_INTS)
+    fpc = _clip_frames(clip_len, N, first, frames_per_clip)
+    bits, nbytes, flags, out, absmax = _p0_encode_buffers(lib, n_clips * fpc, N, C, bits, little_endian, raw_be_ints, out, absmax,
+                                                          clips.device)
     with torch.cuda.device(clips.device):
         lib.p0_analogue_clips(clips.data_ptr() + first * C * clips.element_size(), code, n_clips, clip_len, fpc, N, C, bits, flags,
                               out.data_ptr(), out.stride(0), absmax.data_ptr(),
@@ -179,9 +188,9 @@ def digital_clips(payload: torch.Tensor, out: torch.Tensor, N: int, bits: int, l
         raise ValueError("out must be float64 [n_clips, clip_len, C]")
     lib = _lib.load()
     n_clips, clip_len, C = out.shape
-    fpc = (clip_len - first) // N if frames_per_clip is None else frames_per_clip
-    if fpc < 1 or first < 0 or first + fpc * N > clip_len or payload.shape[0] < n_clips * fpc:
-        raise ValueError("the frames do not fit the clip / the payload batch")
+    fpc = _clip_frames(clip_len, N, first, frames_per_clip)
+    if payload.shape[0] < n_clips * fpc:
+        raise ValueError("the frames do not fit the payload batch")
     flags = int(little_endian) * _lib.FRAD_LITTLE_ENDIAN
     with torch.cuda.device(out.device):
         lib.p0_digital_clips(payload.data_ptr(), payload.stride(0), n_clips, fpc, N, C, bits, flags,
@@ -200,13 +209,16 @@ def overflow_scan(absmax: torch.Tensor, bits: int, flag: torch.Tensor) -> None:
         _lib.load().p0_overflow_scan(absmax.data_ptr(), absmax.numel(), bits, flag.data_ptr(), _stream_ptr())
 
 
-def crc32_frames(payload: torch.Tensor, nbytes: int) -> torch.Tensor:
+def crc32_frames(payload: torch.Tensor, nbytes: int, out: torch.Tensor | None = None) -> torch.Tensor:
     """zlib.crc32 of ``payload[i, :nbytes]`` for every row, as int32 bit patterns on the device
-    (the checksum ASFH.write stores in a lossless frame header, tools/asfh.py:51-73)."""
-    _require_cuda_any(payload, "payload")
+    (the checksum ASFH.write stores in a lossless frame header, tools/asfh.py:51-73); into ``out`` int32 [n_frames] if given."""
+    _require_cuda(payload, "payload", contiguous=False)
     if payload.dtype != torch.uint8 or payload.dim() != 2 or payload.stride(1) != 1 or payload.shape[1] < nbytes:
         raise ValueError("payload must be a uint8 [n_frames, >= nbytes] tensor with unit column stride")
-    out = torch.empty(payload.shape[0], dtype=torch.int32, device=payload.device)
+    if out is None:
+        out = torch.empty(payload.shape[0], dtype=torch.int32, device=payload.device)
+    elif out.dtype != torch.int32 or out.shape != payload.shape[:1] or out.device != payload.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int32 [{payload.shape[0]}] tensor on {payload.device}")
     with torch.cuda.device(payload.device):
         _lib.load().crc32_frames(payload.data_ptr(), payload.stride(0), payload.shape[0], nbytes, out.data_ptr(), _stream_ptr())
     return out
@@ -223,7 +235,7 @@ def _require_rs_ratio(dsize: int, codesize: int):
 
 
 def _require_rows(t: torch.Tensor, width: int, what: str):
-    _require_cuda_any(t, what)
+    _require_cuda(t, what, contiguous=False)
     if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < width or (t.shape[0] > 1 and t.stride(0) < width):
         raise ValueError(f"{what} must be a uint8 [n_frames, >= {width}] tensor with unit column stride and rows >= {width} bytes apart")
 
@@ -248,30 +260,76 @@ def rs_encode_frames(payload: torch.Tensor, nbytes: int, dsize: int, codesize: i
     return out[:, :P]
 
 
+def _require_ragged(src: torch.Tensor, offsets: torch.Tensor, what: str) -> int:
+    """The static half of a ragged batch's check -- ``src`` uint8 [total] and ``offsets`` int64 [n_frames + 1], contiguous on
+    one device, frame i at ``src[offsets[i]:offsets[i + 1]]`` -- without looking at a value.  -> n_frames"""
+    _require_cuda(src, what); _require_cuda(offsets, "offsets")
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or offsets.device != src.device:
+        raise ValueError(f"offsets must be a 1-D int64 tensor of n_frames + 1 entries on the device of {what}")
+    return offsets.numel() - 1
+
+
+def _require_offsets_within(src: torch.Tensor, offsets: torch.Tensor, *more) -> list:
+    """The other half: the offsets do not decrease and stay within ``src``, so no caller buffer reaches a kernel unchecked.
+    This is the operator's one device-to-host read; ``more`` (0-d int64 tensors) ride along and come back as integers."""
+    lo, hi, mono, *more = torch.stack([offsets.min(), offsets.max(), (offsets[1:] < offsets[:-1]).any().to(torch.int64), *more]).tolist()
+    if lo < 0 or hi > src.numel() or mono:
+        raise ValueError(f"offsets must be non-decreasing and within [0, {src.numel()}] (got min {lo}, max {hi})")
+    return more
+
+
+def _require_frame_count(n_frames: int, what: str):
+    if n_frames > 0x7fffffff:
+        raise ValueError(f"at most 2^31 - 1 {what} per batch")
+
+
+def _rs_pointers(packed: torch.Tensor, head: int, n_frames: int) -> list:
+    _require_cuda(packed, "packed")
+    return [packed.data_ptr() + o for o in ecc.pack_layout(head, n_frames)]
+
+
+def rs_encode_packed(packed: torch.Tensor, head: int, n_frames: int, n_blocks: int, dsize: int, codesize: int, out: torch.Tensor):
+    """frad_rs_encode over ``packed``, the uploaded buffer of ``ecc.pack(payloads, dsize, codesize, False)`` (``head``,
+    ``n_blocks`` as it returned them): ecc.encode of payload i to ``out[out_off[i]:out_off[i + 1]]`` (uint8, contiguous)."""
+    _require_cuda(out, "out")
+    with torch.cuda.device(packed.device):
+        _lib.load().rs_encode(*_rs_pointers(packed, head, n_frames), n_frames, n_blocks, dsize, codesize, out.data_ptr(), _stream_ptr())
+    return out
+
+
+def rs_repair_packed(packed: torch.Tensor, head: int, n_frames: int, n_blocks: int, dsize: int, codesize: int, out: torch.Tensor):
+    """frad_rs_repair over the uploaded ``ecc.pack(payloads, dsize, codesize, True)``: the repaired data part of payload i to
+    ``out[out_off[i]:out_off[i + 1]]``.  -> int32 [2 * n_frames]: corrected blocks per payload, then failed blocks per payload"""
+    _require_cuda(out, "out")
+    counts = torch.empty(2 * n_frames + n_blocks + 1, dtype=torch.int32, device=packed.device)    # corrected, failed, work list
+    c = counts.data_ptr()
+    with torch.cuda.device(packed.device):
+        _lib.load().rs_repair(*_rs_pointers(packed, head, n_frames), n_frames, n_blocks, dsize, codesize, out.data_ptr(),
+                              c, c + 4 * n_frames, c + 8 * n_frames, _stream_ptr())
+    return counts[:2 * n_frames]
+
+
 def crc16_ansi_frames(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     """common.crc16_ansi of ``data[offsets[i]:offsets[i + 1]]`` for every frame, as int16 bit patterns on the device (the
     checksum a compact-profile ECC header stores, tools/asfh.py).  The offsets are checked against ``data`` before the launch
     (one small device-to-host read)."""
-    _require_cuda(data, "data"); _require_cuda(offsets, "offsets")
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("data must be a 1-D uint8 tensor")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or offsets.device != data.device:
-        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries on the device of data")
-    n = offsets.numel() - 1
-    if n and not bool(((offsets[1:] >= offsets[:-1]).all() & (offsets[0] >= 0) & (offsets[-1] <= data.numel())).item()):
-        raise ValueError("offsets must be non-decreasing and within data")
+    n = _require_ragged(data, offsets, "data")
+    _require_offsets_within(data, offsets)
     out = torch.empty(n, dtype=torch.int16, device=data.device)
     with torch.cuda.device(data.device):
         _lib.load().crc16_ansi_frames(data.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), _stream_ptr())
     return out
 
 
-def _pcm_out_tensor(fmt: str, shape, device) -> torch.Tensor:
-    """uint8 storage for `shape` elements of PCM format `fmt` (torch has no big-endian or unsigned 16/32/64 dtypes)"""
-    n = 1
+def _pcm_out_tensor(fmt: str, shape, device, slack: int = 0) -> torch.Tensor:
+    """uint8 storage for `shape` elements of PCM format `fmt` (torch has no big-endian or unsigned 16/32/64 dtypes), with
+    ``slack`` allocated bytes behind it that the tensor does not show"""
+    n = itemsize_of(pcm_dtype_code(fmt))
     for d in shape:
         n *= d
-    return torch.empty(n * itemsize_of(pcm_dtype_code(fmt)), dtype=torch.uint8, device=device)
+    return torch.empty(n + slack, dtype=torch.uint8, device=device)[:n] if slack else torch.empty(n, dtype=torch.uint8, device=device)
 
 
 def from_f64(pcm: torch.Tensor, out_format: str, *, raw_be_ints: bool = True) -> torch.Tensor:
@@ -336,9 +394,7 @@ def p1_analogue_batch(pcm: torch.Tensor, pcm_format: str, n_frames: int, N: int,
     code = pcm_dtype_code(pcm_format)
     hop = N if frame_stride is None else frame_stride
     nv = N if n_valid is None else n_valid
-    need = ((n_frames - 1) * hop + nv) * C * itemsize_of(code) if n_frames else 0
-    if pcm.numel() * pcm.element_size() < need:
-        raise ValueError(f"pcm holds {pcm.numel() * pcm.element_size()} bytes, {need} needed")
+    _require_pcm_span(pcm, n_frames, hop, nv, C, code)
     q = torch.empty((n_frames, N, C), dtype=torch.int32, device=pcm.device)
     tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=pcm.device)
     flags = int(raw_be_ints) * _lib.FRAD_RAW_BE_INTS
@@ -346,6 +402,49 @@ def p1_analogue_batch(pcm: torch.Tensor, pcm_format: str, n_frames: int, N: int,
         lib.p1_analogue(pcm.data_ptr(), code, n_frames, N, C, hop, nv, bits, srate, float(loss_level), flags,
                         q.data_ptr(), tq.data_ptr(), _stream_ptr())
     return q, tq
+
+
+def golomb_bound(profile: int, N: int, C: int) -> int:
+    """upper bound of one frame's pre-deflate body, a multiple of 16 (frad_p1_golomb_bound / frad_p2_golomb_bound)"""
+    lib = _lib.load()
+    return lib.p1_golomb_bound(N, C) if profile == 1 else lib.p2_golomb_bound(N, C)
+
+
+def rows_offsets(rows: torch.Tensor, nbytes: torch.Tensor) -> torch.Tensor:
+    """The scan pass of frad_rows_compact: ``rows`` uint8 [n, stride] of which row i holds ``nbytes[i]`` (int64) bytes ->
+    ``offsets`` int64 [n + 1], the rows' places when laid back to back; ``offsets[-1]`` (for the caller to read) is their total."""
+    n, stride = rows.shape
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.load().rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, 0, offsets.data_ptr(), _stream_ptr())
+    return offsets
+
+
+def rows_gather(rows: torch.Tensor, nbytes: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The gather pass of frad_rows_compact: row i's bytes to ``out[offsets[i]:offsets[i + 1]]``, ``offsets`` from
+    ``rows_offsets`` and ``out`` a contiguous uint8 tensor of at least ``offsets[-1]`` bytes (the caller has read the total)."""
+    n, stride = rows.shape
+    with torch.cuda.device(rows.device):
+        _lib.load().rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n, out.data_ptr(), offsets.data_ptr(), _stream_ptr())
+    return out
+
+
+def _golomb_encode(profile: int, q: torch.Tensor, *ints) -> tuple[torch.Tensor, torch.Tensor]:
+    """frad_p{1,2}_golomb_encode into rows of the bound's length, then the rows laid back to back -> (bodies, offsets)"""
+    _require_cuda(q, "q")
+    for t in ints:
+        _require_cuda(t, "tq / lpc")
+    n_frames, N, C = q.shape
+    lib = _lib.load()
+    stride = golomb_bound(profile, N, C)
+    rows = torch.empty((n_frames, stride), dtype=torch.uint8, device=q.device)
+    nbytes = torch.empty(n_frames, dtype=torch.int64, device=q.device)
+    with torch.cuda.device(q.device):
+        (lib.p1_golomb_encode if profile == 1 else lib.p2_golomb_encode)(
+            q.data_ptr(), *(t.data_ptr() for t in ints), n_frames, N, C, rows.data_ptr(), stride, nbytes.data_ptr(), _stream_ptr())
+    offsets = rows_offsets(rows, nbytes)
+    total = int(offsets[-1].item()) if n_frames else 0      # the one host read: the size of the result
+    return rows_gather(rows, nbytes, offsets, torch.empty(total, dtype=torch.uint8, device=q.device)), offsets
 
 
 def p1_golomb_encode_batch(q: torch.Tensor, tq: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -357,28 +456,13 @@ def p1_golomb_encode_batch(q: torch.Tensor, tq: torch.Tensor) -> tuple[torch.Ten
     _require_cuda(q, "q"); _require_cuda(tq, "tq")
     if q.dtype != torch.int32 or tq.dtype != torch.int32 or not q.is_contiguous() or not tq.is_contiguous():
         raise TypeError("q and tq must be contiguous int32")
-    n_frames, N, C = q.shape
-    lib = _lib.load()
-    stride = lib.p1_golomb_bound(N, C)
-    rows = torch.empty((n_frames, stride), dtype=torch.uint8, device=q.device)
-    nbytes = torch.empty(n_frames, dtype=torch.int64, device=q.device)
-    offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=q.device)
-    with torch.cuda.device(q.device):
-        lib.p1_golomb_encode(q.data_ptr(), tq.data_ptr(), n_frames, N, C, rows.data_ptr(), stride, nbytes.data_ptr(), _stream_ptr())
-        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, 0, offsets.data_ptr(), _stream_ptr())
-        total = int(offsets[-1].item()) if n_frames else 0      # the one host read: the size of the result
-        out = torch.empty(total, dtype=torch.uint8, device=q.device)
-        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, out.data_ptr(), offsets.data_ptr(), _stream_ptr())
-    return out, offsets
+    return _golomb_encode(1, q, tq)
 
 
 def p1_golomb_decode_batch(bodies: torch.Tensor, offsets: torch.Tensor, N: int, C: int):
     """The two ``exp_golomb_rice_decode`` calls + ``untrim`` of ``profile1.digital`` (profile1.py:59-64,
     p1tools.py:62-74): inflated bodies (uint8, frame i at ``offsets[i]:offsets[i+1]``) -> ``(q, tq, status)``."""
-    _require_cuda(bodies, "bodies"); _require_cuda(offsets, "offsets")
-    if bodies.dtype != torch.uint8 or offsets.dtype != torch.int64:
-        raise TypeError("bodies must be uint8 and offsets int64")
-    n_frames = offsets.numel() - 1
+    n_frames = _require_ragged(bodies, offsets, "bodies")   # (no look at the values: that would be a host read in the decoder's run)
     q = torch.empty((n_frames, N, C), dtype=torch.int32, device=bodies.device)
     tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=bodies.device)
     status = torch.empty(max(n_frames, 1), dtype=torch.int32, device=bodies.device)
@@ -416,10 +500,7 @@ def p2_golomb_decode_batch(bodies: torch.Tensor, offsets: torch.Tensor, N: int, 
     """The three ``exp_golomb_rice_decode`` calls + ``untrim`` of ``profile2.digital`` (profile2.py:64-76): inflated bodies
     (uint8, frame i at ``offsets[i]:offsets[i+1]``, 8 readable bytes after the last) -> ``(q [n, N, C], tq [n, 27, C],
     lpc [n, 13, C], status [n])``; status 1 = the body's prefix does not fit (decoded as a frame of zeros)."""
-    _require_cuda(bodies, "bodies"); _require_cuda(offsets, "offsets")
-    if bodies.dtype != torch.uint8 or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise ValueError("bodies must be uint8 and offsets a 1-D int64 tensor of n_frames + 1 entries")
-    n_frames = offsets.numel() - 1
+    n_frames = _require_ragged(bodies, offsets, "bodies")   # (as p1_golomb_decode_batch: static only)
     q = torch.empty((n_frames, N, C), dtype=torch.int32, device=bodies.device)
     tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=bodies.device)
     lpc = torch.empty((n_frames, P2_LPC, C), dtype=torch.int32, device=bodies.device)
@@ -461,9 +542,7 @@ def p2_analogue_batch(pcm: torch.Tensor, pcm_format: str, n_frames: int, N: int,
     nv = N if n_valid is None else n_valid
     if n_frames < 0 or hop < 0 or not 0 <= nv <= N:
         raise ValueError(f"bad frame geometry: n_frames={n_frames} frame_stride={hop} n_valid={nv} N={N}")
-    need = ((n_frames - 1) * hop + nv) * C * itemsize_of(code) if n_frames else 0
-    if pcm.numel() * pcm.element_size() < need:
-        raise ValueError(f"pcm holds {pcm.numel() * pcm.element_size()} bytes, {need} needed")
+    _require_pcm_span(pcm, n_frames, hop, nv, C, code)
     _require_cuda(pcm, "pcm")
     q = torch.empty((n_frames, N, C), dtype=torch.int32, device=pcm.device)
     tq = torch.empty((n_frames, P1_BANDS, C), dtype=torch.int32, device=pcm.device)
@@ -484,20 +563,7 @@ def p2_golomb_encode_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor)
     n_frames, N, C = q.shape
     _require_int32(tq, (n_frames, P1_BANDS, C), "tq")
     _require_int32(lpc, (n_frames, P2_LPC, C), "lpc")
-    _require_cuda(q, "q"); _require_cuda(tq, "tq"); _require_cuda(lpc, "lpc")
-    lib = _lib.load()
-    stride = lib.p2_golomb_bound(N, C)
-    rows = torch.empty((n_frames, stride), dtype=torch.uint8, device=q.device)
-    nbytes = torch.empty(n_frames, dtype=torch.int64, device=q.device)
-    offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=q.device)
-    with torch.cuda.device(q.device):
-        lib.p2_golomb_encode(q.data_ptr(), tq.data_ptr(), lpc.data_ptr(), n_frames, N, C, rows.data_ptr(), stride, nbytes.data_ptr(),
-                             _stream_ptr())
-        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, 0, offsets.data_ptr(), _stream_ptr())
-        total = int(offsets[-1].item()) if n_frames else 0      # the one host read: the size of the result
-        out = torch.empty(total, dtype=torch.uint8, device=q.device)
-        lib.rows_compact(rows.data_ptr(), stride, nbytes.data_ptr(), n_frames, out.data_ptr(), offsets.data_ptr(), _stream_ptr())
-    return out, offsets
+    return _golomb_encode(2, q, tq, lpc)
 
 
 def p2_digital_batch(q: torch.Tensor, tq: torch.Tensor, lpc: torch.Tensor, N: int, C: int, bits: int, srate: int) -> torch.Tensor:
@@ -525,9 +591,8 @@ def p1_overlap_add(frames: torch.Tensor, overlap_ratio: int, prev_tail: torch.Te
     pt = prev_tail.data_ptr() if prev_tail is not None else 0
     with torch.cuda.device(frames.device):
         if out_format is not None and out_format not in ("f64le",):
-            code = pcm_dtype_code(out_format)
-            out = torch.empty(n_frames * cut * C * itemsize_of(code) + 16, dtype=torch.uint8, device=frames.device)[:n_frames * cut * C * itemsize_of(code)]
-            _lib.load().p1_overlap_add_pcm(frames.data_ptr(), n_frames, N, C, overlap_ratio, pt, code, out.data_ptr(), nxt.data_ptr(), _stream_ptr())
+            out = _pcm_out_tensor(out_format, (n_frames, cut, C), frames.device, slack=16)
+            _lib.load().p1_overlap_add_pcm(frames.data_ptr(), n_frames, N, C, overlap_ratio, pt, pcm_dtype_code(out_format), out.data_ptr(), nxt.data_ptr(), _stream_ptr())
         else:
             out = torch.empty((n_frames, cut, C), dtype=torch.float64, device=frames.device)
             _lib.load().p1_overlap_add(frames.data_ptr(), n_frames, N, C, overlap_ratio, pt, out.data_ptr(), nxt.data_ptr(), _stream_ptr())
@@ -593,8 +658,7 @@ def clips_overlap_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, 
     if out_format is None:
         out = torch.empty((total, C), dtype=torch.float64, device=device)
     else:
-        nb = total * C * itemsize_of(code)
-        out = torch.empty(nb + 16, dtype=torch.uint8, device=device)[:nb]
+        out = _pcm_out_tensor(out_format, (total, C), device, slack=16)
     if total == 0 or n_clips == 0:
         return out, out_off
     # the four index tables (and the window) in one upload: int64 clip_frame0 | out_off | tail_off | float64 window | int32 tail_rows
@@ -631,22 +695,12 @@ def inflate_batch(src: torch.Tensor, offsets: torch.Tensor, dst_stride: int):
     first ``dst_bytes[i]`` bytes equal ``zlib.decompress(stream_i, wbits=-15)``; status 1 = zlib rejects the stream, 2 = the
     output would exceed ``dst_stride`` bytes.  ``dst_stride`` a positive multiple of 16.  The offsets are checked against
     ``src`` here (one device-to-host read), so no caller buffer reaches the kernel unchecked."""
-    _require_cuda(src, "src"); _require_cuda(offsets, "offsets")
-    if src.dtype != torch.uint8 or src.dim() != 1:
-        raise ValueError(f"src must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries")
-    if offsets.device != src.device:
-        raise ValueError("src and offsets must be on the same device")
+    n_frames = _require_ragged(src, offsets, "src")
     dst_stride = int(dst_stride)
     if dst_stride < 16 or dst_stride % 16:
         raise ValueError(f"dst_stride must be a positive multiple of 16, got {dst_stride}")
-    n_frames = offsets.numel() - 1
-    if n_frames > 0x7fffffff:
-        raise ValueError("at most 2^31 - 1 streams per batch")
-    lo, hi, mono = torch.stack([offsets.min(), offsets.max(), (offsets[1:] < offsets[:-1]).any().to(torch.int64)]).tolist()
-    if lo < 0 or hi > src.numel() or mono:
-        raise ValueError(f"offsets must be non-decreasing and within [0, {src.numel()}] (got min {lo}, max {hi})")
+    _require_frame_count(n_frames, "streams")
+    _require_offsets_within(src, offsets)
     # + 16 bytes behind the last row: frad_rows_compact reads a row as aligned words, one word beyond its bytes
     dst = torch.empty(n_frames * dst_stride + 16, dtype=torch.uint8, device=src.device)
     nbytes = torch.empty(max(n_frames, 1), dtype=torch.int64, device=src.device)
@@ -675,21 +729,10 @@ def deflate_batch(src: torch.Tensor, offsets: torch.Tensor):
     (``DEFLATE_HOST``) = the body is ``DEFLATE_LIMIT`` bytes or longer and is left to the host (nothing written to its row).
     The stride is chosen from the longest body, with 4 bytes to spare for ``frad_rows_compact``'s word reads.  The offsets
     are checked against ``src`` here (one device-to-host read), so no caller buffer reaches the kernel unchecked."""
-    _require_cuda(src, "src"); _require_cuda(offsets, "offsets")
-    if src.dtype != torch.uint8 or src.dim() != 1:
-        raise ValueError(f"src must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise ValueError("offsets must be a 1-D int64 tensor of n_frames + 1 entries")
-    if offsets.device != src.device:
-        raise ValueError("src and offsets must be on the same device")
-    n_frames = offsets.numel() - 1
-    if n_frames > 0x7fffffff:
-        raise ValueError("at most 2^31 - 1 bodies per batch")
-    lens = offsets[1:] - offsets[:-1]
-    longest = lens.max() if n_frames else torch.zeros((), dtype=torch.int64, device=src.device)
-    lo, hi, mono, longest = torch.stack([offsets.min(), offsets.max(), (lens < 0).any().to(torch.int64), longest]).tolist()
-    if lo < 0 or hi > src.numel() or mono:
-        raise ValueError(f"offsets must be non-decreasing and within [0, {src.numel()}] (got min {lo}, max {hi})")
+    n_frames = _require_ragged(src, offsets, "src")
+    _require_frame_count(n_frames, "bodies")
+    longest = (offsets[1:] - offsets[:-1]).max() if n_frames else torch.zeros((), dtype=torch.int64, device=src.device)
+    longest, = _require_offsets_within(src, offsets, longest)             # (the longest body rides along in the one host read)
     lib = _lib.load()
     stride = lib.deflate_stride(min(longest, DEFLATE_LIMIT - 1) + 4)
     dst = torch.empty(max(n_frames * stride, 16), dtype=torch.uint8, device=src.device)

@@ -81,3 +81,9 @@ def pack(payloads: list, dsize: int, codesize: int, repair: bool):
         buf[:nin] = np.frombuffer(b"".join(payloads), np.uint8)
     buf[head:] = np.concatenate([in_off, blk_off, out_off]).view(np.uint8)
     return buf, head, int(blk_off[-1]), out_off
+
+
+def pack_layout(head: int, n: int) -> tuple:
+    """byte offsets of (payloads, in_off, blk_off, out_off) in ``pack``'s buffer of n payloads: the four pointers of
+    frad_rs_encode / frad_rs_repair once the buffer's address is added"""
+    return 0, head, head + 8 * (n + 1), head + 16 * (n + 1)

@@ -6,14 +6,13 @@ from __future__ import annotations
 
 import struct
 import sys
-import zlib
 
 import numpy as np
 
 from .backend.pcmformat import ff_format_to_numpy_type
 from .fourier import AVAILABLE, BIT_DEPTHS, SEGMAX, profiles
 from .fourier.profiles import compact
-from .frames import map_zlib
+from .frames import map_zlib, raw_deflate
 from .tools.asfh import ASFH
 
 
@@ -83,10 +82,7 @@ class Encoder:
             prot, crcs = self.bridge.rs_encode(payloads, dsize, cs, crc32=True)
         return [self._head(idx, fsize).write(p, crc=c) for (_, idx, fsize), p, c in zip(items, prot, crcs)]
 
-    @staticmethod
-    def _deflate(body: bytes) -> bytes:
-        co = zlib.compressobj(zlib.Z_DEFAULT_COMPRESSION, zlib.DEFLATED, -15)     # profile1.py:50 wbits=-15
-        return co.compress(body) + co.flush()
+    _deflate = staticmethod(raw_deflate)                                          # profile1.py:50 wbits=-15
 
     def _encode_frames(self, pcm: bytes, n_frames: int, n_eff: int, hop: int, n_valid: int) -> bytes:
         """n_frames frames of n_eff sample-frames, frame i starting i*hop sample-frames into `pcm`."""

@@ -108,6 +108,12 @@ def map_zlib(fn, items: list) -> list:
     return out
 
 
+def raw_deflate(body: bytes) -> bytes:
+    """the reference's zlib.compress(body, wbits=-15) (profile1.py:50, profile2.py:54): level 6, no wrapper"""
+    co = zlib.compressobj(zlib.Z_DEFAULT_COMPRESSION, zlib.DEFLATED, -15)
+    return co.compress(body) + co.flush()
+
+
 def _inflate(frad: bytes):
     try:
         return zlib.decompress(frad, wbits=-15)

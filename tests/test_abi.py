@@ -73,3 +73,34 @@ def test_baseline_path_kernels_keep_their_registers():
         hit = [k for k in rows if name in k]
         assert hit, name
         assert max(rows[k] for k in hit) <= cap, (name, [rows[k] for k in hit])
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    import helpers
+    return _lib.FradLib(helpers.build_emulator())
+
+
+def test_binding_has_a_method_for_every_symbol(emu_lib):
+    for name in _lib.SYMBOLS:
+        assert callable(getattr(emu_lib, name[len("frad_"):])), name
+
+
+def test_every_status_entry_point_takes_its_arguments_and_checks_its_status(emu_lib):
+    """The methods are generated from SYMBOLS (or, a few, written out): each status entry point called with every argument
+    zero and the stream left out either returns None or raises FradError -- a method with a missing or misplaced parameter
+    would raise TypeError or ctypes.ArgumentError instead.  Nothing is launched: every all-zero call is empty or invalid."""
+    status = [name for name, (res, _) in _lib.SYMBOLS.items() if res is _lib.STATUS and name != "frad_plan_prepare"]
+    assert status
+    for name in status:
+        zeros = [0] * (len(_lib.SYMBOLS[name][1]) - 1)
+        try:
+            assert getattr(emu_lib, name[len("frad_"):])(*zeros) is None, name
+        except _lib.FradError as e:
+            assert e.status < 0, name
+
+
+def test_a_failing_status_carries_its_fields(emu_lib):
+    with pytest.raises(_lib.FradError) as e:
+        emu_lib.p0_overflow_scan(0, -1, 16, 0)
+    assert e.value.status == -1

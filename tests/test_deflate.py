@@ -260,6 +260,9 @@ def test_deflate_batch_checks_its_arguments():
     src = torch.zeros(10, dtype=torch.uint8, device="cuda")
     off = torch.tensor([0, 4, 10], dtype=torch.int64, device="cuda")
     core.deflate_batch(src, off)
+    rows, nbytes, status = core.deflate_batch(src[:0], off[:1])          # an empty batch: empty results, nothing launched
+    assert tuple(rows.shape) == (0, 16) and nbytes.dtype == torch.int64 and status.dtype == torch.int32
+    assert nbytes.numel() == 0 and status.numel() == 0
     for bad in (torch.tensor([0, 11], device="cuda"), torch.tensor([0, 6, 4], device="cuda"), torch.tensor([-1, 4], device="cuda")):
         with pytest.raises(ValueError):
             core.deflate_batch(src, bad)
@@ -343,6 +346,9 @@ def test_device_deflate_large_frames_take_the_host_route():
     for profile in (1, 2):
         got, enc = _same_streams(profile, pcm, 4, 28672, 2, loss=0.125)
         assert enc.bridge.last_deflate_host >= 1
+    import torch
+    none = torch.zeros(0, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+    assert enc.bridge.deflate_payloads(*none) == []                       # no bodies: no payloads, nothing launched
 
 
 @pytest.mark.gpu

@@ -135,6 +135,7 @@ def test_known_answer_model():
 
 def test_known_answer_kernels(bk):
     assert bk.rs_encode([b"hello world"], 245, 10) == [HELLO]
+    assert bk.rs_encode([], 245, 10) == [] and bk.rs_encode([], 245, 10, crc32=True) == ([], [])    # no payloads: nothing launched
     damaged = bytearray(HELLO)
     damaged[0] ^= 0x55; damaged[7] ^= 1; damaged[-1] ^= 0xFF
     fixed, cor, bad = bk.rs_repair([bytes(damaged), HELLO], 245, 10)

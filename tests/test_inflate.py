@@ -361,6 +361,9 @@ def test_inflate_batch_checks_its_arguments():
     src = torch.zeros(10, dtype=torch.uint8, device="cuda")
     off = torch.tensor([0, 4, 10], dtype=torch.int64, device="cuda")
     core.inflate_batch(src, off, 32)
+    rows, nbytes, status = core.inflate_batch(src[:0], off[:1], 32)      # an empty batch: empty results, nothing launched
+    assert tuple(rows.shape) == (0, 32) and nbytes.dtype == torch.int64 and status.dtype == torch.int32
+    assert nbytes.numel() == 0 and status.numel() == 0
     with pytest.raises(ValueError):
         core.inflate_batch(src, off, 24)
     with pytest.raises(ValueError):

@@ -375,6 +375,8 @@ def test_cfg2_sized_batch_round_trips_on_the_device():
     q, tq, lpc = core.p2_analogue_batch(pcm, "s16le", n, N, C, 16, 48000, 0.5)
     assert int((lpc != 0).any(dim=1).any(dim=1).sum()) > n // 2
     flat, off = core.p2_golomb_encode_batch(q, tq, lpc)
+    none, off0 = core.p2_golomb_encode_batch(q[:0], tq[:0], lpc[:0])      # an empty batch: no bytes and the one offset
+    assert none.dtype == torch.uint8 and none.numel() == 0 and off0.dtype == torch.int64 and off0.numel() == 1
     flat_s = torch.cat([flat, torch.zeros(16, dtype=torch.uint8, device=flat.device)])
     q2, tq2, lpc2, st = core.p2_golomb_decode_batch(flat_s, off, N, C)
     assert torch.equal(q, q2) and torch.equal(tq, tq2) and torch.equal(lpc, lpc2) and not st.any()

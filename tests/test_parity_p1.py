@@ -257,6 +257,12 @@ def test_golomb_known_answers_and_long_vectors(be, g6):
 def test_golomb_random_round_trip_and_decoder_end_conditions(be):
     rng = np.random.default_rng(77)
     F, N, C = (3, 640, 2) if be.name == "emu" else (40, 2048, 2)
+    if be.name == "gpu":                                    # the operator on an empty batch: no bytes and the one offset
+        import torch
+        from frad_python_amd import core
+        none, off0 = core.p1_golomb_encode_batch(torch.zeros((0, N, C), dtype=torch.int32, device="cuda"),
+                                                 torch.zeros((0, 27, C), dtype=torch.int32, device="cuda"))
+        assert none.dtype == torch.uint8 and none.numel() == 0 and off0.dtype == torch.int64 and off0.numel() == 1
     q = np.rint(rng.laplace(0, 5.0, (F, N, C)) * rng.integers(0, 2, (F, N, 1))).astype(np.int32)
     q[0] = 0; q[1, 5:] = 0                                     # all-zero frame (k = 0), long zero tail
     tq = rng.integers(0, 40, (F, 27, C)).astype(np.int32)
