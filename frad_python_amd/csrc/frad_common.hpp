@@ -11,13 +11,6 @@
 
 namespace frad {
 
-typedef unsigned long long u64;
-// plain compiler vectors for 8/16-byte global accesses (HIP's uint4/double2 are classes and cannot be
-// accessed through an address-space qualified pointer)
-typedef uint32_t v4u __attribute__((vector_size(16)));
-typedef uint32_t v2u __attribute__((vector_size(8)));
-typedef double v2d __attribute__((vector_size(16)));
-
 // ---------------------------------------------------------------------------------------------
 // bit casts
 // ---------------------------------------------------------------------------------------------
@@ -347,6 +340,20 @@ __device__ __forceinline__ uint32_t payload_byte(int64_t s, int bits, bool le, i
     return code_byte(code_of(i), bits, le, j);
 }
 
+// team-level synchronisation: lanes of one wave run in lockstep and the LDS serves a wave's
+// instructions in order, so a team that fits in a wave only needs the compiler kept honest.
+template <int TEAM, bool LDSONLY = false> __device__ __forceinline__ void team_sync() {
+    if constexpr (TEAM <= 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else if constexpr (LDSONLY) {
+        FRAD_LDS_BARRIER();                      // pipelined kernels: do not drain global loads/stores
+    } else {
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // |x| max with numpy semantics: the bit pattern of |x| is monotone in the value for non-NaN and
 // every NaN pattern is larger than +Inf, so an unsigned max reproduces np.max(np.abs(.)) incl.
@@ -354,35 +361,26 @@ __device__ __forceinline__ uint32_t payload_byte(int64_t s, int bits, bool le, i
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u64 abs_bits(double v) { return d2u(v) & 0x7fffffffffffffffULL; }
 
-// Wave-wide butterfly all-reduce (xor 1, 2, 4, 8, 16, 32) of a 64-bit value.  On gfx950 the first four steps are DPP
-// moves -- quad_perm for xor 1 / 2, row_half_mirror and row_mirror for xor 4 / 8 (their partners hold the same value as
-// the xor partners once the smaller groups are uniform) -- and the last two read one lane per 16-lane row through
-// SGPRs, so no step goes through the LDS crossbar (a ds_bpermute pair per step otherwise).  The emulator runs the
-// plain xor butterfly; both combine the same operands in the same order.
-#ifndef FRAD_HOST_EMULATION
-template <int CTRL> __device__ __forceinline__ u64 dpp_move_u64(u64 v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, false);
-    return (u64)(uint32_t)lo | ((u64)(uint32_t)hi << 32);
-}
-__device__ __forceinline__ u64 read_lane_u64(u64 v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return (u64)lo | ((u64)hi << 32);
-}
-#endif
+// Wave-wide butterfly all-reduce (xor 1, 2, 4, 8, 16, 32) of a 64-bit value: the seam's all-reduce inside the four rows
+// of 16 lanes (frad_platform.hpp), then one lane per row.  `op` is commutative in its bits.
 template <class Op> __device__ __forceinline__ u64 wave_allreduce_u64(u64 v, Op op) {
-#ifdef FRAD_HOST_EMULATION
-    for (int off = 1; off < 64; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-    return v;
-#else
-    v = op(v, dpp_move_u64<0xB1>(v));                        // quad_perm [1,0,3,2]
-    v = op(v, dpp_move_u64<0x4E>(v));                        // quad_perm [2,3,0,1]
-    v = op(v, dpp_move_u64<0x141>(v));                       // row_half_mirror
-    v = op(v, dpp_move_u64<0x140>(v));                       // row_mirror
-    const u64 r0 = read_lane_u64(v, 0), r1 = read_lane_u64(v, 16), r2 = read_lane_u64(v, 32), r3 = read_lane_u64(v, 48);
+    FRAD_ROWS16_ALLREDUCE_U64(v, op)
+    const u64 r0 = wave_row_u64(v, 0), r1 = wave_row_u64(v, 1), r2 = wave_row_u64(v, 2), r3 = wave_row_u64(v, 3);
     return op(op(r0, r1), op(r2, r3));
-#endif
+}
+// the same over the two 32-lane halves of a wave: lanes 0-31 -> lo, lanes 32-63 -> hi (all lanes get both)
+template <class Op> __device__ __forceinline__ void half_wave_allreduce_u64(u64 v, u64& lo, u64& hi, Op op) {
+    FRAD_ROWS16_ALLREDUCE_U64(v, op)
+    lo = op(wave_row_u64(v, 0), wave_row_u64(v, 1));
+    hi = op(wave_row_u64(v, 2), wave_row_u64(v, 3));
+}
+__device__ __forceinline__ void half_wave_max_u64(u64 v, u64& lo, u64& hi) {
+    half_wave_allreduce_u64(v, lo, hi, [](u64 a, u64 b) { return b > a ? b : a; });
+}
+__device__ __forceinline__ void half_wave_sum_f64(double v, double& lo, double& hi) {
+    u64 l, h;
+    half_wave_allreduce_u64(d2u(v), l, h, [](u64 a, u64 b) { return d2u(u2d(a) + u2d(b)); });
+    lo = u2d(l); hi = u2d(h);
 }
 
 __device__ __forceinline__ u64 wave_max_u64(u64 v) {

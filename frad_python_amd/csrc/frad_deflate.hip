@@ -63,6 +63,8 @@ __host__ __device__ __forceinline__ DfLayout df_layout(int maxb, bool gwin) {
     return l;
 }
 
+// as team_sync<64>() but with workgroup-scope fences, which also wait for the wave's LDS traffic (s_waitcnt lgkmcnt(0)):
+// the instruction sequence this kernel was verified with
 __device__ __forceinline__ void wsync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();

@@ -8,7 +8,7 @@
 // radix-R butterflies on them (R <= 16) and exchanges through LDS between passes.  No MFMA:
 // the work is a bandwidth-bound butterfly network, not a dense contraction.
 #pragma once
-#include "frad_platform.hpp"
+#include "frad_common.hpp"
 
 namespace frad {
 
@@ -120,20 +120,6 @@ template <int R, bool INV, typename T> __device__ __forceinline__ void dft(cx<T>
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int c = a + 1; c < 4; ++c) { cx<T> t = v[4 * a + c]; v[4 * a + c] = v[4 * c + a]; v[4 * c + a] = t; }
-    }
-}
-
-// team-level synchronisation: lanes of one wave run in lockstep and the LDS serves a wave's
-// instructions in order, so a team that fits in a wave only needs the compiler kept honest.
-template <int TEAM, bool LDSONLY = false> __device__ __forceinline__ void team_sync() {
-    if constexpr (TEAM <= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else if constexpr (LDSONLY) {
-        FRAD_LDS_BARRIER();                      // pipelined kernels: do not drain global loads/stores
-    } else {
-        __syncthreads();
     }
 }
 

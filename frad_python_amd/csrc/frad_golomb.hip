@@ -292,7 +292,8 @@ constexpr int DPITCH = DCW + 1;            // row pitch in words: odd, so equal 
 constexpr int DEC_LDS = 64 * DPITCH * 4;
 
 __device__ __forceinline__ int32_t sat32(long long v) { return v > 2147483647LL ? 2147483647 : v < -2147483648LL ? (int32_t)(-2147483647 - 1) : (int32_t)v; }
-__device__ __forceinline__ bool wave_any(bool v) { return wave_allreduce_u64(v ? 1ull : 0ull, [](u64 a, u64 b) { return a | b; }) != 0; }
+// (an all-reduce, not the seam's ballot wave_any: kept as the instruction sequence these kernels were measured with)
+__device__ __forceinline__ bool wave_any_reduce(bool v) { return wave_allreduce_u64(v ? 1ull : 0ull, [](u64 a, u64 b) { return a | b; }) != 0; }
 
 // the calling lane's stream: bytes [p, p + len) = k byte + code bits; out[0 .. cap) receives the values, zero-filled
 // (inlined, and the LDS taken from the kernel's own symbol: a pointer that went through a real call is generic, FLAT
@@ -318,7 +319,7 @@ __device__ __forceinline__ void decode_stream_wave(const unsigned char* p, long 
     long long n_out = 0;
     const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;    // four values per 16-byte store
     int32_t o0 = 0, o1 = 0, o2 = 0;
-    for (long long round = 0; wave_any(active); ++round) {
+    for (long long round = 0; wave_any_reduce(active); ++round) {
         // ---- fill: row r <- words [round * DCW, +DCW) of lane r's stream, big-endian to MSB-first; 16 rows' loads in
         // flight at a time (one load instruction per row: 64 lanes x 4 bytes, coalesced)
         for (int r0 = 0; r0 < 64; r0 += 16) {
@@ -640,7 +641,7 @@ __device__ __forceinline__ bool decode_stream_2phase(const unsigned char* p, lon
             for (int round = 0;; ++round) {
                 const int ex = (int)__shfl((unsigned long long)(unsigned)my_x, lane ? lane - 1 : 0, 64);
                 const bool redo = mine && lane > 0 && ex != my_entry;
-                if (!wave_any(redo)) break;
+                if (!wave_any_reduce(redo)) break;
                 if (round >= 16) return false;                            // (uniform) a stream that keeps its chunks out of step: slow kernel
                 if (redo) my_entry = ex;
                 walk(my_entry, redo, my_x, my_cnt, true, my_re);
@@ -648,20 +649,20 @@ __device__ __forceinline__ bool decode_stream_2phase(const unsigned char* p, lon
             // Every lane now starts where its left neighbour ended.  A lane whose last walk realigned has not walked the code as it is
             // written (a stream with longer zero prefixes than the reference coder makes, or a damaged one): those walk again, exactly,
             // and the corrections repeat with exact walks.
-            if (wave_any(mine && my_re)) {
+            if (wave_any_reduce(mine && my_re)) {
                 bool dummy = false;
                 walk(my_entry, mine && my_re, my_x, my_cnt, false, dummy);
                 for (int round = 0;; ++round) {
                     const int ex = (int)__shfl((unsigned long long)(unsigned)my_x, lane ? lane - 1 : 0, 64);
                     const bool redo = mine && lane > 0 && ex != my_entry;
-                    if (!wave_any(redo)) break;
+                    if (!wave_any_reduce(redo)) break;
                     if (round >= 16) return false;
                     if (redo) my_entry = ex;
                     walk(my_entry, redo, my_x, my_cnt, false, dummy);
                 }
             }
             // ---- phase 2: output index of every chunk's first code ------------------------------------------------------
-            if (wave_any(mine && my_x == (int)GW_LONG)) return false;     // (uniform) a code beyond 32 bits on the path
+            if (wave_any_reduce(mine && my_x == (int)GW_LONG)) return false;     // (uniform) a code beyond 32 bits on the path
             if (!mine) my_cnt = 0;
             my_base = my_cnt;
             for (int off = 1; off < 64; off <<= 1) {

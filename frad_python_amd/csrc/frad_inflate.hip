@@ -52,14 +52,6 @@ constexpr int L_IN = L_DH + (int)sizeof(HTab);             // u32 [IF_IW]
 constexpr int L_WIN = L_IN + 4 * IF_IW;                    // output window
 static_assert(L_WIN % 16 == 0 && sizeof(HTab) % 16 == 0, "LDS layout");
 
-// lanes of one wave run in lockstep and the LDS serves a wave's instructions in order: only the compiler is kept from
-// moving LDS accesses across this point (the emulator's lanes do need the barrier)
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ uint32_t bitrev(uint32_t v, int n) {            // the low n bits of v, reversed
     v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
     v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
@@ -85,7 +77,7 @@ __device__ __forceinline__ int clen_order(int i) {                         // RF
 template <int ROOT>
 __device__ __forceinline__ bool build_code(const unsigned char* lens, int nwords, bool lenient, HTab* h, unsigned short* tab,
                                            unsigned short* work, int lane) {
-    wsync();                                                   // the previous block's lookups are done
+    team_sync<64>();                                                   // the previous block's lookups are done
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lens);
     // lane l (1..15) counts the codes of length l: four lengths per (broadcast) LDS read
     int cnt = 0;
@@ -94,7 +86,7 @@ __device__ __forceinline__ bool build_code(const unsigned char* lens, int nwords
         cnt += ((int)(v & 255u) == lane) + ((int)((v >> 8) & 255u) == lane) + ((int)((v >> 16) & 255u) == lane) + ((int)(v >> 24) == lane);
     }
     if (lane >= 1 && lane < 16) h->cnt[lane] = cnt;
-    wsync();
+    team_sync<64>();
     int left = 1, maxl = 0, code = 0, off = 0, my_first = 0, my_off = 0;
     bool over = false;
     for (int l = 1; l < 16; ++l) {                             // uniform: the same 15 broadcast reads in every lane
@@ -119,7 +111,7 @@ __device__ __forceinline__ bool build_code(const unsigned char* lens, int nwords
                 if ((int)((v >> (8 * b)) & 255u) == lane && lane != 0) work[at++] = (unsigned short)(4 * w + b);
         }
     }
-    wsync();
+    team_sync<64>();
     // primary table: entry e holds the code of <= ROOT bits that is a prefix of e's bits, found per length (lanes split
     // the entries, the lengths are uniform)
     constexpr int PER = (1 << ROOT) / 64;
@@ -138,7 +130,7 @@ __device__ __forceinline__ bool build_code(const unsigned char* lens, int nwords
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) tab[lane + 64 * k] = (unsigned short)ent[k];
-    wsync();
+    team_sync<64>();
     return true;
 }
 
@@ -190,7 +182,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
     auto need = [&](long long lo, long long hi) {              // words [lo, hi) must be loaded; hi - lo <= IF_IW
         if (whi >= hi || whi >= nin) return;
         const long long nh = lo + IF_IW < nin ? lo + IF_IW : nin;
-        wsync();                                               // every lane is done with the words being replaced
+        team_sync<64>();                                               // every lane is done with the words being replaced
         for (long long k = (whi > lo ? whi : lo) + lane; k < nh; k += 64) {
             const long long b = 4 * k;
             uint32_t v = 0;
@@ -200,7 +192,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
             in32[k & (IF_IW - 1)] = v;
         }
         whi = nh;
-        wsync();
+        team_sync<64>();
     };
     auto peek = [&](long long bp) -> uint32_t {                // 32 input bits from bit bp (loaded: words bp/32 and bp/32 + 1)
         const long long w = bp >> 5;
@@ -214,7 +206,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
     int tabs = 0;                                              // 1: the fixed code's tables are built
     // RING: write ring bytes [flushed, flushed + n) to the row (flushed and the row 16-byte aligned)
     auto write_out = [&](long long n) {
-        wsync();
+        team_sync<64>();
         const long long full = n & ~15LL;
         for (long long j = 16 * lane; j < full; j += 1024) {
             const v4u v = *reinterpret_cast<const v4u*>(win + ((flushed + j) & WMASK));
@@ -223,7 +215,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
         if (lane < n - full) row[flushed + full + lane] = win[(flushed + full + lane) & WMASK];
         flushed += n;
         fenced = pos;                                          // (the barrier above made every byte so far visible)
-        wsync();                                               // the ring bytes written out may now be overwritten
+        team_sync<64>();                                               // the ring bytes written out may now be overwritten
     };
     bool last = false;
     while (st == 0 && !last) {
@@ -255,7 +247,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
         HTab* const dhp = dh;
         if (type == 1) {                                       // ---- fixed code
             if (tabs != 1) {
-                wsync();
+                team_sync<64>();
                 for (int i = lane; i < 320; i += 64) lens[i] = (unsigned char)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
                 build_code<IF_LROOT>(lens, 72, true, lh, ltab, lwork, lane);
                 build_code<IF_DROOT>(lens + IF_DIST_AT, 8, true, dhp, dtab, dwork, lane);
@@ -268,17 +260,17 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
             const int nlen = (int)(h14 & 31u) + 257, ndist = (int)((h14 >> 5) & 31u) + 1, ncode = (int)((h14 >> 10) & 15u) + 4;
             bp += 14;
             if (nlen > 286 || ndist > 30) { st = 1; break; }
-            wsync();                                           // (the previous block's tables and lengths are no longer read)
+            team_sync<64>();                                           // (the previous block's tables and lengths are no longer read)
             for (int i = lane; i < 320; i += 64) lens[i] = 0;
             if (lane < 32) clens[lane] = 0;
-            wsync();
+            team_sync<64>();
             for (int i = 0; i < ncode; ++i) {                  // uniform; lane 0 stores
                 need(bp >> 5, (bp >> 5) + 4);
                 const uint32_t c3 = peek(bp) & 7u;
                 if (lane == 0) clens[clen_order(i)] = (unsigned char)c3;
                 bp += 3;
             }
-            wsync();
+            team_sync<64>();
             if (!build_code<IF_CROOT>(clens, 5, false, lh, ltab, lwork, lane)) { st = 1; break; }
             int have = 0, prev = -1;
             const int total = nlen + ndist;
@@ -307,7 +299,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
                 prev = val;
             }
             if (st) break;
-            wsync();
+            team_sync<64>();
             if (lens[256] == 0) { st = 1; break; }             // no end-of-block code
             if (!build_code<IF_LROOT>(lens, 72, true, lh, ltab, lwork, lane)) { st = 1; break; }
             if (!build_code<IF_DROOT>(lens + IF_DIST_AT, 8, true, dhp, dtab, dwork, lane)) { st = 1; break; }
@@ -353,14 +345,14 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
             if (dist > pos) { st = 1; break; }
             if (pos + mlen > cap) { st = 2; break; }
             // every source byte is older than this copy; make the ones written since the last fence visible to all lanes
-            if (pos - dist + (dist < mlen ? dist : mlen) > fenced) { wsync(); fenced = pos; }
+            if (pos - dist + (dist < mlen ? dist : mlen) > fenced) { team_sync<64>(); fenced = pos; }
             unsigned char v[5];
 #pragma unroll
             for (int t = 0; t < 5; ++t) {
                 const int j = lane + 64 * t;
                 v[t] = j < mlen ? win[(pos - dist + (dist >= mlen ? j : j % (int)dist)) & WMASK] : 0;
             }
-            if (RING) wsync();                                 // a ring slot read above may be one this copy writes
+            if (RING) team_sync<64>();                                 // a ring slot read above may be one this copy writes
 #pragma unroll
             for (int t = 0; t < 5; ++t) {
                 const int j = lane + 64 * t;
@@ -373,7 +365,7 @@ __global__ void __launch_bounds__(64) k_inflate(const unsigned char* __restrict_
     if (st == 0) {
         if (RING) write_out(pos - flushed);
         else {
-            wsync();
+            team_sync<64>();
             const long long full = pos & ~15LL;
             for (long long j = 16 * lane; j < full; j += 1024) *FRAD_GPTR(v4u, row + j) = *reinterpret_cast<const v4u*>(win + j);
             if (lane < pos - full) row[full + lane] = win[full + lane];

@@ -14,9 +14,6 @@
 #pragma once
 #include "frad_kernels.hpp"
 #include <type_traits>
-#ifdef FRAD_HOST_EMULATION
-#include <thread>
-#endif
 
 namespace frad {
 
@@ -462,18 +459,6 @@ k_p0_inv_pers(const unsigned char* __restrict__ payload, double* __restrict__ ou
 // unit's staging overlaps another's butterflies and a third one's stores, while the 32 KiB of
 // tables in LDS are still shared by all of them.
 // =============================================================================================
-#ifndef FRAD_HOST_EMULATION
-#define FRAD_LDS_ADD(p, v) __hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define FRAD_LDS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define FRAD_NAP() __builtin_amdgcn_s_sleep(1)
-#define FRAD_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-#define FRAD_LDS_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_SEQ_CST)
-#define FRAD_LDS_LOAD(p) __atomic_load_n((p), __ATOMIC_SEQ_CST)
-#define FRAD_NAP() std::this_thread::yield()
-#define FRAD_LGKM0() __atomic_thread_fence(__ATOMIC_SEQ_CST)
-#endif
-
 // barrier over the NW waves of a unit; `ctr` is the unit's LDS word, `epoch` a per-thread count
 template <int NW> __device__ __forceinline__ void unit_barrier(unsigned* ctr, unsigned& epoch) {
     if constexpr (NW == 1) {
@@ -483,7 +468,7 @@ template <int NW> __device__ __forceinline__ void unit_barrier(unsigned* ctr, un
         __builtin_amdgcn_wave_barrier();                     // (lockstep on hardware; orders the emulator's lanes)
         FRAD_LGKM0();                                        // this wave's LDS traffic is done
         if ((threadIdx.x & 63) == 0) FRAD_LDS_ADD(ctr, 1u);
-        while (FRAD_LDS_LOAD(ctr) < epoch) FRAD_NAP();       // every arrival is a +1; never reset
+        while (FRAD_LDS_LOAD(ctr) < epoch) FRAD_NAP(1);      // every arrival is a +1; never reset
         FRAD_LGKM0();
     }
 }

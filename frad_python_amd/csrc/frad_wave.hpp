@@ -91,92 +91,75 @@ __device__ __forceinline__ void tw32_apply(cx<T> (&o)[16]) {          // o[n] *=
 // address registers per wave instead of ~100.
 __device__ __forceinline__ int pslot(int r, int c) { return 34 * r + 2 * (c & 15) + (c >> 4); }
 
-// Diagnostic build only (-DFRAD_WAVE_STAMPS): per-phase shader-clock totals of wave 0 of every block, summed into
-// g_wave_stamps[phase] (cycles, phases 0 .. 11) and g_wave_stamps[15] (units); no stamp executes in the product build.
-#if defined(FRAD_WAVE_STAMPS) && !defined(FRAD_HOST_EMULATION)
+// ---- compile-time switches of this file ---------------------------------------------------------------------------------
+// None is defined in the product build; every one is a -D flag of a diagnostic or experiment build (tools/build_variant.sh),
+// gfx950 only.  The target-specific primitives themselves live in the seam (frad_platform.hpp); the switches are applied
+// here, where the kernels call them.
+//   diagnostics (default: not defined)
+//     FRAD_WAVE_STAMPS         per-phase shader-clock totals of every wave, read by frad_debug_wave_stamps (tools/stamps.py)
+//     FRAD_ASM_MARKS           section marks in the assembly for tools/asm_stats.py (-S builds; the scheduler will not move
+//                              code across a mark)
+//     FRAD_X_NODMA             encode: no LDS-DMA of the raw PCM (the kernel computes on stale bytes)
+//     FRAD_X_NOTW              encode: pass-1 twiddles are constants instead of LDS reads
+//     FRAD_X_NOCOMPUTE         encode: staged bytes go straight back out, no transform
+//     FRAD_X_NOEXCH            encode: no exchange through LDS between the passes
+//     FRAD_X_NOPTAB            encode: pair-step tables are constants instead of LDS reads
+//     FRAD_WAVE_NOSTORE        encode: the payload row stores are kept in the code but never execute
+//     FRAD_WAVE_PLAIN_STORES   stream_store is a plain store instead of a nontemporal one
+//     FRAD_WAVE_PLAIN_LOADS    decode: payload words come by plain loads instead of nontemporal ones
+//   tunables (default in brackets)
+//     FRAD_WAVE_DMA_AUX [2]    cache-policy bits of the LDS-DMA (2 = nontemporal: the PCM is read once)
+//     FRAD_WAVE_TWB [4]        rows of TW1 per double-buffered twiddle batch
+//     FRAD_WAVE_JOBFENCE [1]   read by no code: the experiment (profiles/r03_ablations.txt) was not kept, its build flag still compiles
+//     FRAD_WAVE_PRB [4]        exchange-plane pairs per double-buffered read batch
+#ifndef FRAD_WAVE_DMA_AUX
+#define FRAD_WAVE_DMA_AUX 2
+#endif
+#ifndef FRAD_WAVE_TWB
+#define FRAD_WAVE_TWB 4
+#endif
+#ifndef FRAD_WAVE_JOBFENCE
+#define FRAD_WAVE_JOBFENCE 1
+#endif
+#ifndef FRAD_WAVE_PRB
+#define FRAD_WAVE_PRB 4
+#endif
+
+// FRAD_WAVE_STAMPS: per-phase shader-clock totals of wave 0 of every block, summed into g_wave_stamps[phase] (cycles,
+// phases 0 .. 11) and g_wave_stamps[15] (units); no stamp executes in the product build.
+#ifdef FRAD_WAVE_STAMPS
 __device__ unsigned long long g_wave_stamps[16];
-#define FRAD_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_last; st_last = t_; } while (0)
-#define FRAD_STAMP_DECL unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime(), st_units = 0
+#define FRAD_STAMP(i) do { const unsigned long long t_ = FRAD_CLOCK(); st_acc[i] += t_ - st_last; st_last = t_; } while (0)
+#define FRAD_STAMP_UNIT() (++st_units)
+#define FRAD_STAMP_DECL unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = FRAD_CLOCK(), st_units = 0
 #define FRAD_STAMP_FLUSH do { if ((threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_wave_stamps[i_], st_acc[i_]); atomicAdd(&g_wave_stamps[15], st_units); } } while (0)
 #else
 #define FRAD_STAMP(i) ((void)0)
+#define FRAD_STAMP_UNIT() ((void)0)
 #define FRAD_STAMP_DECL ((void)0)
 #define FRAD_STAMP_FLUSH ((void)0)
 #endif
-
-// section marks for tools/asm_stats.py: a comment in the assembly, no instruction -- but an asm statement the scheduler will not
-// move code across, so diagnostic builds only (hipcc -DFRAD_ASM_MARKS --cuda-device-only -S ...)
-#if defined(FRAD_ASM_MARKS) && !defined(FRAD_HOST_EMULATION)
-#define FRAD_MARK(name) asm volatile("; FRAD_MARK " name)
+#ifdef FRAD_ASM_MARKS
+#define FRAD_MARK(name) FRAD_ASM_COMMENT("FRAD_MARK " name)
 #else
 #define FRAD_MARK(name) ((void)0)
 #endif
+
 // work distribution inside a block: one LDS word, bumped by lane 0 of a wave and broadcast
-#ifndef FRAD_HOST_EMULATION
-#define FRAD_WAVE_LDS_ADD(p, v) __hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define FRAD_WAVE_BCAST0(x) ((unsigned)__builtin_amdgcn_readfirstlane((int)(x)))
-#define FRAD_WAVE_SLEEP(n) __builtin_amdgcn_s_sleep(n)
-#else
-#define FRAD_WAVE_LDS_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_SEQ_CST)
-#define FRAD_WAVE_BCAST0(x) ((unsigned)__shfl((unsigned long long)(x), 0, 64))
-#define FRAD_WAVE_SLEEP(n) ((void)0)
-#endif
 __device__ __forceinline__ long long wave_next_unit(unsigned* ctr) {
     unsigned v = 0;
-    if ((threadIdx.x & 63) == 0) v = FRAD_WAVE_LDS_ADD(ctr, 1u);
-    return (long long)FRAD_WAVE_BCAST0(v);
+    if ((threadIdx.x & 63) == 0) v = FRAD_LDS_ADD(ctr, 1u);
+    return (long long)(unsigned)wave_uniform_int((int)v);
 }
 
-#ifndef FRAD_HOST_EMULATION
 #define FRAD_WAVE_BOUNDS __launch_bounds__(64 * kWaveWaves, 2)
-#else
-#define FRAD_WAVE_BOUNDS
-#endif
-
-// maxima of the two 32-lane halves of a wave (all lanes get both)
-__device__ __forceinline__ void half_wave_max_u64(u64 v, u64& lo, u64& hi) {
-    auto op = [](u64 a, u64 b) { return b > a ? b : a; };
-#ifdef FRAD_HOST_EMULATION
-    for (int off = 1; off < 32; off <<= 1) v = op(v, __shfl_xor(v, off, 64));
-    const u64 other = __shfl_xor(v, 32, 64);
-    const bool up = (threadIdx.x & 32) != 0;
-    lo = up ? other : v; hi = up ? v : other;
-#else
-    v = op(v, dpp_move_u64<0xB1>(v));
-    v = op(v, dpp_move_u64<0x4E>(v));
-    v = op(v, dpp_move_u64<0x141>(v));
-    v = op(v, dpp_move_u64<0x140>(v));
-    lo = op(read_lane_u64(v, 0), read_lane_u64(v, 16));
-    hi = op(read_lane_u64(v, 32), read_lane_u64(v, 48));
-#endif
-}
-
-// running max of |v| in one instruction (fmax(fm, fabs(v)) costs two: the compiler canonicalises the operand first)
-__device__ __forceinline__ void absmax_acc(double& fm, double v) {
-#ifdef FRAD_HOST_EMULATION
-    fm = fmax(fm, fabs(v));
-#else
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(fm) : "v"(fm), "v"(v));
-#endif
-}
 
 // 16-byte store of data that is written once and not read again by this kernel (payload rows, decoded PCM): nontemporal
 __device__ __forceinline__ void stream_store(unsigned char* p, v4u v) {
-#if defined(FRAD_HOST_EMULATION) || defined(FRAD_WAVE_PLAIN_STORES)
+#ifdef FRAD_WAVE_PLAIN_STORES
     *FRAD_GPTR(v4u, p) = v;
 #else
-    __builtin_nontemporal_store(v, FRAD_GPTR(v4u, p));
-#endif
-}
-
-// bytes of `v` picked by a v_perm_b32 selector (selector bytes 4..7 address v's bytes 0..3)
-__device__ __forceinline__ uint32_t wave_perm(uint32_t v, uint32_t sel) {
-#ifdef FRAD_HOST_EMULATION
-    uint32_t r = 0;
-    for (int i = 0; i < 4; ++i) { const uint32_t s = (sel >> (8 * i)) & 0xffu; r |= (s >= 4 && s < 8 ? (v >> (8 * (s - 4))) & 0xffu : 0u) << (8 * i); }
-    return r;
-#else
-    return __builtin_amdgcn_perm(v, 0u, sel);
+    FRAD_NT_STORE(v, FRAD_GPTR(v4u, p));
 #endif
 }
 
@@ -187,18 +170,9 @@ __device__ __forceinline__ double wave_elem(uint32_t word, int shift) {
     if constexpr (EB == 32) {
         return cvt_pcm_c<double, CODE, RAW, true>((u64)word);
     } else if constexpr (kind == 1 && !be) {                 // signed little-endian: one v_bfe_i32 + one conversion
-#ifdef FRAD_HOST_EMULATION
-        const int s = (int)((word >> shift) << (32 - EB)) >> (32 - EB);
-#else
-        const int s = __builtin_amdgcn_sbfe((int)word, (unsigned)shift, (unsigned)EB);
-#endif
-        return (double)s;
+        return (double)bfe_i32(word, shift, EB);
     } else {
-#ifdef FRAD_HOST_EMULATION
-        const uint32_t r = (word >> shift) & ((1u << EB) - 1u);
-#else
-        const uint32_t r = __builtin_amdgcn_ubfe(word, (unsigned)shift, (unsigned)EB);
-#endif
+        const uint32_t r = bfe_u32(word, shift, EB);
         return cvt_pcm_c<double, CODE, RAW, true>((u64)r);
     }
 }
@@ -276,13 +250,6 @@ __device__ __forceinline__ double p1w_quant(double x) {        // sign(x) |x|^0.
 // a reciprocal, two square roots, four products), so unless it lies within that distance of a half-integer it rounds to
 // the same integer as the float64 value; the rare undecided bin (about y x 3e-6 of them) takes the exact path.  The
 // result is therefore identical to the float64 arithmetic's, at a quarter of its instructions.
-__device__ __forceinline__ float p1w_sqrtf(float v) {
-#ifdef FRAD_HOST_EMULATION
-    return sqrtf(v);
-#else
-    return __builtin_amdgcn_sqrtf(v);
-#endif
-}
 __device__ __forceinline__ int32_t p1w_quantise(double x, double div, double scale) {
     const float xf = (float)x, df = (float)div;
     if (div == 0.0) return 0;                                 // x / inf -> +-0 -> 0
@@ -331,45 +298,6 @@ __device__ __forceinline__ double p1_band_threshold(double energy, int bins, dou
 // =============================================================================================
 #define FRAD_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-// sums over the two 32-lane halves of a wave (all lanes get both)
-__device__ __forceinline__ void half_wave_sum_f64(double v, double& lo, double& hi) {
-#ifdef FRAD_HOST_EMULATION
-    for (int off = 1; off < 32; off <<= 1) v = v + u2d(__shfl_xor(d2u(v), off, 64));
-    const double other = u2d(__shfl_xor(d2u(v), 32, 64));
-    const bool up = (threadIdx.x & 32) != 0;
-    lo = up ? other : v; hi = up ? v : other;
-#else
-    v = v + u2d(dpp_move_u64<0xB1>(d2u(v)));
-    v = v + u2d(dpp_move_u64<0x4E>(d2u(v)));
-    v = v + u2d(dpp_move_u64<0x141>(d2u(v)));
-    v = v + u2d(dpp_move_u64<0x140>(d2u(v)));
-    lo = u2d(read_lane_u64(d2u(v), 0)) + u2d(read_lane_u64(d2u(v), 16));
-    hi = u2d(read_lane_u64(d2u(v), 32)) + u2d(read_lane_u64(d2u(v), 48));
-#endif
-}
-__device__ __forceinline__ int wave_read_lane(int v, int src) {      // v of lane `src` (wave-uniform index), as a scalar
-#ifdef FRAD_HOST_EMULATION
-    return (int)__shfl((unsigned long long)(unsigned)v, src, 64);
-#else
-    return __builtin_amdgcn_readlane(v, src);
-#endif
-}
-__device__ __forceinline__ bool wave_any(bool b) {                     // true in some lane (all 64 lanes call it)
-#ifdef FRAD_HOST_EMULATION
-    unsigned long long v = b ? 1 : 0;
-    for (int off = 1; off < 64; off <<= 1) v |= __shfl_xor(v, off, 64);
-    return v != 0;
-#else
-    return __builtin_amdgcn_ballot_w64(b) != 0;
-#endif
-}
-__device__ __forceinline__ int wave_uniform_int(int v) {
-#ifdef FRAD_HOST_EMULATION
-    return (int)__shfl((unsigned long long)(unsigned)v, 0, 64);
-#else
-    return __builtin_amdgcn_readfirstlane(v);
-#endif
-}
 // ---- K7 tail (round 3): Z (E, O as pass 2 leaves them) -> quantised integers ---------------------------------------
 // profile1.py:21-40, p1tools.py:15-44.  The DCT pair step runs ONCE and leaves the frame's 4096 coefficients in the
 // registers that held E / O (lane 0's different pairing is resolved by one permutation up front, so all 16 jobs read the
@@ -396,28 +324,7 @@ __device__ __forceinline__ P1K7Lds p1w_k7_lds(unsigned char* smem) {
     return {b, reinterpret_cast<const int*>(b + 2048), reinterpret_cast<const double*>(b + 2048 + 128), reinterpret_cast<const unsigned short*>(b + 2048 + 128 + 256),
             reinterpret_cast<const double*>(b + 2048 + 128 + 256 + 4096)};
 }
-// float32 hardware transcendentals (one instruction each, about 1 ulp): seeds and decisions only, never a stored value
-__device__ __forceinline__ float k7_log2f(float v) {
-#ifdef FRAD_HOST_EMULATION
-    return log2f(v);
-#else
-    return __builtin_amdgcn_logf(v);
-#endif
-}
-__device__ __forceinline__ float k7_exp2f(float v) {
-#ifdef FRAD_HOST_EMULATION
-    return exp2f(v);
-#else
-    return __builtin_amdgcn_exp2f(v);
-#endif
-}
-__device__ __forceinline__ float k7_rcpf(float v) {
-#ifdef FRAD_HOST_EMULATION
-    return 1.0f / v;
-#else
-    return __builtin_amdgcn_rcpf(v);
-#endif
-}
+// (k7_log2f, k7_exp2f, k7_rcpf, p1w_sqrtf: the seam's approximate float32 instructions -- seeds and decisions only, never a stored value)
 // r^0.4 = sqrt(r)^0.8 (p1tools.py:30, r = mean of the squared band), float64 to a few ulp without libm (whose constants the
 // compiler hoists out of the frame loop into registers it then spills): float32 seed, two Newton steps on y^5 = r^2, the
 // division inside a step by a float32 reciprocal (it scales a correction of relative size 1e-5 and 1e-11).  That reciprocal is of
@@ -637,9 +544,7 @@ __device__ __forceinline__ void wave_p1_tail(cx<T> (&E)[16], cx<T> (&O)[16], con
         XH[s][0] = *reinterpret_cast<const T*>(plw + paddr(k));
         XH[s][1] = *reinterpret_cast<const T*>(plw + paddr(kb3));
     }
-#ifndef FRAD_HOST_EMULATION
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // every plane read has returned: the DMA may land in [8 KiB, 16 KiB)
-#endif
+    FRAD_LGKM0();                                                 // every plane read has returned: the DMA may land in [8 KiB, 16 KiB)
     team_sync<64>();
     FRAD_FENCE();
     dma_next();
@@ -799,18 +704,6 @@ __device__ __forceinline__ void wave_p1_tail(cx<T> (&E)[16], cx<T> (&O)[16], con
         FRAD_FENCE();
     }
 }
-#ifndef FRAD_WAVE_DMA_AUX
-#define FRAD_WAVE_DMA_AUX 2                     // nt: the PCM is read once
-#endif
-#ifndef FRAD_WAVE_TWB
-#define FRAD_WAVE_TWB 4
-#endif
-#ifndef FRAD_WAVE_JOBFENCE
-#define FRAD_WAVE_JOBFENCE 1
-#endif
-#ifndef FRAD_WAVE_PRB
-#define FRAD_WAVE_PRB 4
-#endif
 
 // CLIPS: the batch is a set of equally cut clips (Geom::fpc, clip_stride; frad_p0_analogue_clips) -- a variant of its own, so
 // that the flat batch keeps its frame stride in one scalar product (the clip arithmetic cost the headline kernel its registers)
@@ -847,11 +740,7 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
     }
     const cx<T>* ltab = reinterpret_cast<const cx<T>*>(smem);
     if constexpr (MODE == 1) p1w_tables_to_lds(smem, pw);
-#ifdef FRAD_HOST_EMULATION
-    const int wv = threadIdx.x >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // provably wave-uniform: unit numbers and frame bases stay in SGPRs
-#endif
+    const int wv = wave_uniform_int((int)(threadIdx.x >> 6));   // provably wave-uniform: unit numbers and frame bases stay in SGPRs
     unsigned char* wbuf = smem + kWaveTableBytes + wv * kWaveBufBytes;
     const long long frameb = (g.frame_stride * CC) << LG;
     [[maybe_unused]] const long long gapb = ((g.clip_stride - (long long)g.fpc * g.frame_stride) * CC) << LG;   // bytes skipped between clips
@@ -880,13 +769,8 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
             const unsigned char* src = pcm + frame_off(frame_of(u, h)) + (CC == 2 ? lane : l) * 16;
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) {
-#ifdef FRAD_HOST_EMULATION
-                *reinterpret_cast<v4u*>(wbuf + RAWOFF + i * 1024 + lane * 16) = *reinterpret_cast<const v4u*>(src + i * (CC == 2 ? 1024 : 512));
-#else
 #ifndef FRAD_X_NODMA
-                __builtin_amdgcn_global_load_lds(FRAD_GCPTR(void, src + i * (CC == 2 ? 1024 : 512)),
-                                                 (__attribute__((address_space(3))) void*)(wbuf + RAWOFF + i * 1024), 16, 0, FRAD_WAVE_DMA_AUX);
-#endif
+                lds_dma16<FRAD_WAVE_DMA_AUX>(src + i * (CC == 2 ? 1024 : 512), wbuf + RAWOFF + i * 1024);
 #endif
             }
         }
@@ -900,7 +784,7 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
     if (u < ue) dma_in(u);
     __syncthreads();                                          // tables and counter are in LDS (the barrier's fence also retires the first DMA)
     if constexpr (MODE == 1) { p1w_k7_tables(smem); __syncthreads(); }
-    for (int i = (wv * 8 + (int)(blockIdx.x & 7)) * g.cg; i > 0; --i) FRAD_WAVE_SLEEP(1);      // start stagger (g.cg x 64 cycles per step; 0 = off)
+    for (int i = (wv * 8 + (int)(blockIdx.x & 7)) * g.cg; i > 0; --i) FRAD_NAP(1);      // start stagger (g.cg x 64 cycles per step; 0 = off)
     FRAD_STAMP_DECL;
     while (u < ue) {
         lane = threadIdx.x & 63; FRAD_OPAQUE(lane);           // per-lane addresses are rebuilt each unit (no LICM register hoard)
@@ -919,11 +803,9 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
 #endif
         };
         if constexpr (STAGED) {
-#ifndef FRAD_HOST_EMULATION
             // this unit's DMA was issued before the previous unit's 4 NB row stores: vector-memory operations retire
             // in order, so at most that many may still be in flight
-            asm volatile("s_waitcnt vmcnt(%0)" :: "i"(4 * NB) : "memory");   // (profile 1: the 16 row stores follow the DMA, and one store of threshold codes before them)
-#endif
+            FRAD_VMCNT(4 * NB);                                // (profile 1: the 16 row stores follow the DMA, and one store of threshold codes before them)
             FRAD_STAMP(0); FRAD_MARK("makhoul_convert");
             team_sync<64>();
 #ifdef FRAD_X_NOCOMPUTE
@@ -1079,9 +961,7 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
             plane(ic<1>{});
 #endif
         }
-#ifndef FRAD_HOST_EMULATION
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every plane read has returned: the DMA may overwrite the planes
-#endif
+        FRAD_LGKM0();                                          // every plane read has returned: the DMA may overwrite the planes
         team_sync<64>();
         FRAD_STAMP(3); FRAD_MARK("pass2");
         FRAD_FENCE();
@@ -1246,9 +1126,7 @@ wave_fwd_body(const unsigned char* __restrict__ pcm, unsigned char* __restrict__
         }                                                      // MODE 0
         team_sync<64>();
         FRAD_STAMP(6); FRAD_MARK("unit_end");
-#if defined(FRAD_WAVE_STAMPS) && !defined(FRAD_HOST_EMULATION)
-        ++st_units;
-#endif
+        FRAD_STAMP_UNIT();
         u = next;
     }
     FRAD_STAMP_FLUSH;
@@ -1283,17 +1161,6 @@ k_p1_fwd_wave(const unsigned char* __restrict__ pcm, int32_t* __restrict__ q, co
 //     XOR-swizzled staging buffer in sample order (Makhoul's permutation undone by the write addresses), come back as
 //     16 bytes per lane and leave as eight coalesced 1 KiB stores -- 32 stores per unit, spread over the output phase.
 // =============================================================================================
-// a + s * b into a register of its own (the compiler's tied v_fmac would keep the result inside the 128-bit load tuple
-// that delivered a and b, i.e. four registers alive for a two-register value)
-__device__ __forceinline__ double fma_free(double s, double b, double a) {
-#ifdef FRAD_HOST_EMULATION
-    return fma(s, b, a);
-#else
-    double r;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(s), "v"(b), "v"(a));
-    return r;
-#endif
-}
 template <typename T> __device__ __forceinline__ cx<T> cmulc(cx<T> a, cx<T> w) {      // a * conj(w)
     return {fma(a.x, w.x, a.y * w.y), fma(a.y, w.x, -(a.x * w.y))};
 }
@@ -1319,11 +1186,7 @@ wave_inv_body(const unsigned char* __restrict__ payload, double* __restrict__ ou
     }
     const cx<T>* ltab = reinterpret_cast<const cx<T>*>(smem);
     if constexpr (MODE == 1) p1w_k8_tables_a(smem, pw, 1.0 / pw.scale);
-#ifdef FRAD_HOST_EMULATION
-    const int wv = threadIdx.x >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#endif
+    const int wv = wave_uniform_int((int)(threadIdx.x >> 6));
     unsigned char* wbuf = smem + kWaveTableBytes + wv * kWaveBufBytes;
     const long long n_units = (g.n_frames + FPW - 1) / FPW;
     const long long ub = n_units * blockIdx.x / gridDim.x, ue = n_units * (blockIdx.x + 1) / gridDim.x;
@@ -1351,19 +1214,12 @@ wave_inv_body(const unsigned char* __restrict__ payload, double* __restrict__ ou
         const unsigned char* pB[2] = {fp + (M - ka) * ES, fp + (M - kb) * ES};                // X[M - k]
         const unsigned char* pD[2] = {fp + (N - ka) * ES, fp + (N - kb) * ES};                // X[N - k]
         auto fetch = [&](const unsigned char* p) -> code_t {
-#if defined(FRAD_HOST_EMULATION) || defined(FRAD_WAVE_PLAIN_LOADS)
-            if constexpr (BITS == 16) return *FRAD_GCPTR(unsigned short, p);
-            else if constexpr (BITS == 32) return *FRAD_GCPTR(uint32_t, p);
-            else return *FRAD_GCPTR(u64, p);
+            using word_t = typename std::conditional<BITS == 16, unsigned short, code_t>::type;
+#ifdef FRAD_WAVE_PLAIN_LOADS
+            return *FRAD_GCPTR(word_t, p);
 #else                                                          // read once: nontemporal (keeps the streams out of each other's way in L2 / MALL)
-            if (g.fpb) {
-                if constexpr (BITS == 16) return *FRAD_GCPTR(unsigned short, p);
-                else if constexpr (BITS == 32) return *FRAD_GCPTR(uint32_t, p);
-                else return *FRAD_GCPTR(u64, p);
-            }
-            if constexpr (BITS == 16) return __builtin_nontemporal_load(FRAD_GCPTR(unsigned short, p));
-            else if constexpr (BITS == 32) return __builtin_nontemporal_load(FRAD_GCPTR(uint32_t, p));
-            else return __builtin_nontemporal_load(FRAD_GCPTR(u64, p));
+            if (g.fpb) return *FRAD_GCPTR(word_t, p);
+            return FRAD_NT_LOAD(FRAD_GCPTR(word_t, p));
 #endif
         };
 #pragma unroll
@@ -1404,19 +1260,11 @@ wave_inv_body(const unsigned char* __restrict__ payload, double* __restrict__ ou
     auto value = [&](code_t c) -> T {                          // stored code -> float64, NaN / Inf -> 0 (profile0.py:62-66)
         if constexpr (BITS == 32) {
             float f = u2f(wave_perm(c, psel));
-#ifdef FRAD_HOST_EMULATION
-            if (!std::isfinite(f)) f = 0.0f;
-#else
-            if (__builtin_amdgcn_classf(f, 0x207)) f = 0.0f;   // class mask: bit 0 signalling NaN, 1 quiet NaN, 2 -Inf, 9 +Inf
-#endif
+            if (nonfinite_f32(f)) f = 0.0f;
             return (T)f;
         } else if constexpr (BITS == 16) {
             float f = f16_bits_to_f32(wave_perm(c, psel) & 0xffffu);
-#ifdef FRAD_HOST_EMULATION
-            if (!std::isfinite(f)) f = 0.0f;
-#else
-            if (__builtin_amdgcn_classf(f, 0x207)) f = 0.0f;
-#endif
+            if (nonfinite_f32(f)) f = 0.0f;
             return (T)f;
         } else {
             const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
@@ -1439,7 +1287,7 @@ wave_inv_body(const unsigned char* __restrict__ payload, double* __restrict__ ou
     if constexpr (MODE == 1) { if (u < ue) tq_pf = tq_fetch(u); }
     __syncthreads();                                          // tables and counter are in LDS
     if constexpr (MODE == 1) { p1w_k8_tables_b(smem, pw); __syncthreads(); }
-    for (int i = (wv * 8 + (int)(blockIdx.x & 7)) * g.cg; i > 0; --i) FRAD_WAVE_SLEEP(1);      // start stagger (g.cg x 64 cycles per step; 0 = off)
+    for (int i = (wv * 8 + (int)(blockIdx.x & 7)) * g.cg; i > 0; --i) FRAD_NAP(1);      // start stagger (g.cg x 64 cycles per step; 0 = off)
     while (u < ue) {
         lane = threadIdx.x & 63; FRAD_OPAQUE(lane);
         const int h = lane >> 5, l = lane & 31;
