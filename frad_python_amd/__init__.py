@@ -12,6 +12,6 @@ from .tools.asfh import ASFH  # noqa: F401
 from .encoder import Encoder, EncodeResult  # noqa: F401
 from .decoder import Decoder, DecodeResult  # noqa: F401
 from .repairer import Repairer  # noqa: F401
-from .batch import decode_batch, BatchResult  # noqa: F401
+from .batch import decode_batch, BatchResult, encode_batch, EncodeBatchResult  # noqa: F401
 
-__all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]
+__all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "encode_batch", "EncodeBatchResult", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]

@@ -1,4 +1,4 @@
-"""``decode_batch``: many independent, complete streams decoded in one device pass.
+"""``decode_batch`` and ``encode_batch``: many independent, complete streams (clips) decoded (encoded) in one device pass.
 
 ``Decoder`` is, like the reference's, a one-stream object: a collection of short clips costs one chain of launches per clip, and
 every clip's flush frame (another ``fsize``) a chain of its own.  Here the streams are scanned together, grouped by frame
@@ -6,15 +6,24 @@ geometry, and the frames of ALL streams of a group go through each device stage 
 ``frad_clips_overlap_add`` then cross-fades inside every clip, appends the flush fragments, converts and writes the ragged
 output.  ``res.pcm[i]`` is bit for bit what a fresh ``Decoder`` returns for stream i when it is driven as the
 reference's caller drives it (src/decoder.py:70-88); a stream that does not have the shape ``Encoder.process`` + ``flush``
-writes is decoded by such a ``Decoder`` and listed in ``res.fallback``."""
+writes is decoded by such a ``Decoder`` and listed in ``res.fallback``.
+
+``encode_batch`` is the counterpart: ``Encoder`` is a one-stream object too, so a set of short clips costs an
+upload, a chain of launches for the whole frames, a second chain for the flush frame and a download per clip.  Here the
+clips are joined, one launch of ``frad_clips_frame_cut`` gathers the whole frames of ALL clips into the contiguous block the
+transform kernels read, their flush frames are gathered by length, and every stage is called once per such group.
+``res.streams[i]`` is byte for byte ``e.process(clip_i).buf + e.flush().buf`` of a fresh ``Encoder`` with the same settings;
+a lossless clip with a frame that needs a deeper format is written by such an ``Encoder`` and listed in ``res.fallback``."""
 from __future__ import annotations
 
 import numpy as np
 
 from .backend.pcmformat import ff_format_to_numpy_type, from_f64
 from .decoder import Decoder
+from .encoder import Encoder
 from .fourier import BIT_DEPTHS
-from .frames import BUILT, DEFLATED, classify, inflate_bodies, repair
+from .fourier.profiles import COMPACT, compact
+from .frames import BUILT, DEFLATED, classify, inflate_bodies, map_zlib, raw_deflate, repair
 
 _SCAN_END, _SCAN_TABLE_FULL = 0, 3                          # include/frad_hip.h
 
@@ -294,4 +303,233 @@ def decode_batch(streams, *, fix_error: bool = False, out_format: str | None = N
             if i is not None:
                 chunk.append(i)
                 size += need
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- encoding
+class EncodeBatchResult:
+    """``streams[i]`` (bytes), ``samples[i]`` (the sum of the two ``EncodeResult.samples``), ``frames[i]``; ``fallback``: the
+    sorted indices that a per-clip ``Encoder`` wrote."""
+
+    def __init__(self, n: int):
+        self.streams = [b""] * n
+        self.samples = [0] * n
+        self.frames = [0] * n
+        self.fallback = []
+
+
+def _host_bytes(clip) -> bytes:
+    return clip.cpu().numpy().tobytes() if hasattr(clip, "cpu") else bytes(clip)
+
+
+def zero_bytes_are_zero(pcm_format: str) -> bool:
+    """All-zero bytes convert to +0.0 (pcmformat.py:34-47): the signed integers and the floats.  A little-endian (or 8-bit)
+    unsigned zero is -1.0 (the bias is subtracted), so padding a frame of such a format with zero bytes is not padding it with
+    silence.  The rule goes by the kind alone: the big-endian unsigned formats, which the reference does not scale (their zero
+    is 0.0 too), are kept with the other unsigned ones -- conservative, and one rule instead of two."""
+    return ff_format_to_numpy_type(pcm_format).kind in "if"
+
+
+class _Clips:
+    """The chunk's PCM, joined: on the device behind a bridge with ``clips_join`` + ``clips_frame_cut`` (one upload, one
+    launch per ``cut``), else a numpy array that ``cut`` slices."""
+
+    def __init__(self, bridge, clips: list, nbytes: list, step: int):
+        self.bridge, self.step = bridge, step
+        self.on_dev = getattr(bridge, "clips_frame_cut", None) is not None and getattr(bridge, "clips_join", None) is not None
+        if self.on_dev:
+            self.src = bridge.clips_join(clips, nbytes)
+        else:
+            self.src = np.frombuffer(b"".join(_host_bytes(c)[:n] for c, n in zip(clips, nbytes)), np.uint8)
+
+    def cut(self, row_src, row_valid, row_len: int):
+        """rows of ``row_len`` sample-frames: ``row_valid[r]`` of them from sample-frame ``row_src[r]`` on, then zero bytes"""
+        if self.on_dev:
+            return self.bridge.clips_frame_cut(self.src, row_src, row_valid, row_len, self.step)
+        out = np.zeros((len(row_src), row_len * self.step), np.uint8)
+        for r, (at, n) in enumerate(zip(row_src, row_valid)):
+            out[r, :n * self.step] = self.src[at * self.step:(at + n) * self.step]
+        return out.tobytes()
+
+
+def _lossless_rows(enc: Encoder, block, n: int, fsize: int):
+    """n equally long lossless frames with their headers, as ``Encoder._encode_frames`` writes them through the bridge's
+    ``lossless_encode_stream``.  -> (take(first, count) -> bytes, None), or (None, the frames that need a deeper format -- all of
+    them when the payload length needs the 64-bit field)"""
+    a, prof, C, bridge = enc.asfh, enc.asfh.profile, enc.channels, enc.bridge
+    depths = BIT_DEPTHS[prof]
+    bits = enc.bit_depth if enc.bit_depth in depths else 16
+    a.bit_depth_index, a.channels, a.fsize, a.srate = depths.index(bits), C, fsize, enc.srate
+    ecc_kw = {"ecc_ratio": (a.ecc_dsize, a.ecc_codesize)} if a.ecc else {}
+    got = bridge.lossless_encode_stream(prof, block, enc.pcm_format_name, n, fsize, C, bits, a.endian, a.lossless_head, **ecc_kw)
+    if got is not None:
+        size = len(got) // n
+        return (lambda first, count: got[first * size:(first + count) * size]), None
+    named = getattr(bridge, "last_escalated", None)            # HipBridge: the first pass has named the frames already
+    if named is None:
+        deeper = [used != bits for _, used in bridge.lossless_encode(prof, block, enc.pcm_format_name, n, fsize, C, bits, a.endian)]
+    else:
+        deeper = [False] * n
+        for i in named:
+            deeper[i] = True
+    return None, (deeper if any(deeper) else [True] * n)
+
+
+def _compact_payloads(enc: Encoder, block, n: int, rows: int) -> list:
+    """n compact frames, rows of ``rows`` sample-frames that are valid throughout (a padded tail: up to the zero bytes the cut
+    wrote) -> their deflated payloads, every stage called once"""
+    prof, depths = enc.asfh.profile, BIT_DEPTHS[enc.asfh.profile]
+    bits = enc.bit_depth if enc.bit_depth in depths else 16
+    args = (block, enc.pcm_format_name, n, compact.get_samples_min_ge(rows), enc.channels, bits, compact.get_valid_srate(enc.srate),
+            enc.loss_level, rows, rows)
+    if enc.device_deflate:
+        return getattr(enc.bridge, f"p{prof}_encode_payloads")(*args)
+    return map_zlib(raw_deflate, getattr(enc.bridge, f"p{prof}_encode_bodies")(*args))
+
+
+def _encode_chunk(enc: Encoder, clips: list, have: list, k: list, t: list, n_eff: int, cut: int, pad_tails: bool, fresh: bytes):
+    """The clips of one chunk -- ``have[j]`` whole sample-frames: ``k[j]`` whole frames of ``n_eff``, ``cut`` apart, and a flush
+    frame of ``t[j]`` -> (streams, deeper): ``deeper`` lists the clips with a lossless frame that needs a deeper format; when
+    there are any, ``streams`` is None and the caller sends the rest again.  ``fresh``: the marker of a clip without a frame, as
+    a header writer that has written nothing makes it (``enc``'s has, from the first chunk on)."""
+    prof, C = enc.asfh.profile, enc.channels
+    is_compact = prof in COMPACT
+    step = enc.pcm_format.itemsize * C
+    src = _Clips(enc.bridge, clips, [h * step for h in have], step)
+    clip_off = np.zeros(len(clips) + 1, np.int64)
+    np.cumsum(have, out=clip_off[1:])
+    first = np.zeros(len(clips) + 1, np.int64)                 # clip j's whole frames are rows first[j] : first[j + 1]
+    np.cumsum(k, out=first[1:])
+    M = int(first[-1])
+    # ---- the tails, grouped: compact ones by the legal frame size they pad to (where zero bytes are silence), else by length
+    groups = {}
+    for j, tj in enumerate(t):
+        if tj:
+            groups.setdefault(compact.get_samples_min_ge(tj) if is_compact and pad_tails else tj, []).append(j)
+    row_src = np.concatenate([clip_off[j] + cut * np.arange(k[j], dtype=np.int64) for j in range(len(clips))]) if M else None
+    tail_at = lambda js: [int(clip_off[j]) + k[j] * cut for j in js]
+    if not is_compact:
+        main, deeper, tails = None, set(), {}
+        if M:
+            main, bad = _lossless_rows(enc, src.cut(row_src, np.full(M, n_eff, np.int32), n_eff), M, n_eff)
+            if bad is not None:
+                deeper.update(j for j in range(len(clips)) if any(bad[first[j]:first[j + 1]]))
+        for length, js in groups.items():
+            take, bad = _lossless_rows(enc, src.cut(tail_at(js), [length] * len(js), length), len(js), length)
+            if bad is not None:
+                deeper.update(j for i, j in enumerate(js) if bad[i])
+            for i, j in enumerate(js):
+                tails[j] = (take, i)
+        if deeper:
+            return None, sorted(deeper)
+        return [(main(int(first[j]), k[j]) if k[j] else b"") + (tails[j][0](tails[j][1], 1) if t[j] else b"")
+                for j in range(len(clips))], []
+    # ---- compact: payloads of every frame, one header pass (Reed-Solomon and the checksums of ALL frames in one call)
+    depths = BIT_DEPTHS[prof]
+    idx = depths.index(enc.bit_depth if enc.bit_depth in depths else 16)
+    pay = _compact_payloads(enc, src.cut(row_src, np.full(M, n_eff, np.int32), n_eff), M, n_eff) if M else []
+    tail_pay = {}
+    for rows, js in groups.items():                            # rows: N_t of a padded group, else the tails' own length
+        for j, p in zip(js, _compact_payloads(enc, src.cut(tail_at(js), [t[j] for j in js], rows), len(js), rows)):
+            tail_pay[j] = p
+    items = []
+    for j in range(len(clips)):
+        items += [(p, idx, n_eff) for p in pay[first[j]:first[j + 1]]]
+        if t[j]:
+            items.append((tail_pay[j], idx, t[j]))
+    made = enc._emit_all(items)
+    marker = {}                                                # force_flush() carries the fsize of the last header written
+    for fsize in {n_eff} | set(t):
+        if fsize:
+            marker[fsize] = enc._head(idx, fsize).force_flush()
+    out, at = [], 0
+    for j in range(len(clips)):
+        n = k[j] + (1 if t[j] else 0)
+        frames = made[at:at + n]
+        at += n
+        # Encoder.inner: a flush frame is followed by a marker of its own, and every flush ends with one
+        out.append(b"".join(frames) + (marker[t[j]] * 2 if t[j] else marker[n_eff] if k[j] else fresh))
+    return out, []
+
+
+def encode_batch(clips, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *,
+                 overlap_ratio: int = 0, loss_level: float = 0.5, little_endian: bool = False, ecc_ratio=None,
+                 allow_profile2: bool = False, device_deflate: bool = False, max_batch_bytes: int = 1 << 30,
+                 bridge=None) -> EncodeBatchResult:
+    """Encode a sequence of complete clips (bytes-like, or 1-D device uint8 tensors that are not copied to the host -- except a
+    clip that falls back: the per-clip ``Encoder`` takes host bytes) of raw interleaved PCM in ``pcm_format``, one stream each.  The arguments mean what the ``Encoder`` constructor's and setters'
+    mean, clamping included; ``ecc_ratio`` None: no ECC, a tuple: ``allow_ecc=True`` + ``set_ecc(True, ratio)``.  What the
+    ``Encoder`` refuses (profile 2 without ``allow_profile2``, its ``verify_*`` messages) is a ``ValueError`` here.
+    ``max_batch_bytes``: the clips are cut into chunks of whole clips whose gathered frames stay below it."""
+    checks = (lambda: None if (profile == 2 and allow_profile2) else Encoder.verify_profile(profile),
+              lambda: Encoder.verify_srate(profile, srate), lambda: Encoder.verify_channels(profile, channels),
+              lambda: Encoder.verify_bit_depth(profile, bit_depth), lambda: Encoder.verify_frame_size(profile, frame_size))
+    for check in checks:
+        e = check()
+        if e is not None:
+            raise ValueError(e)
+    if bridge is None:
+        from .bridge import HipBridge
+        bridge = HipBridge()
+
+    def fresh() -> Encoder:
+        enc = Encoder(profile, srate, channels, bit_depth, frame_size, pcm_format, bridge=bridge, allow_profile2=allow_profile2,
+                      allow_ecc=ecc_ratio is not None, device_deflate=device_deflate)
+        enc.set_overlap_ratio(overlap_ratio)
+        enc.set_loss_level(loss_level)
+        enc.set_little_endian(little_endian)
+        if ecc_ratio is not None:
+            enc.set_ecc(True, ecc_ratio)
+        return enc
+
+    clips = list(clips)
+    res = EncodeBatchResult(len(clips))
+    enc = fresh()                                              # the settings, the header writer and the bridge of the batch
+    untouched = enc.asfh.force_flush()                         # the marker of a clip without a frame: no header written yet
+    is_compact = profile in COMPACT
+    n_eff = compact.get_samples_min_ge(enc.fsize) if is_compact else enc.fsize
+    ratio = enc.asfh.overlap_ratio
+    cut = n_eff * (ratio - 1) // ratio if (is_compact and ratio > 1) else n_eff
+    step = enc.pcm_format.itemsize * channels
+    pad_tails = zero_bytes_are_zero(pcm_format)                # DESIGN.md 4i: unsigned formats group their tails by exact length
+    for c in clips:
+        if hasattr(c, "numel") and (c.dim() != 1 or c.element_size() != 1):
+            raise TypeError("a device clip must be a 1-D uint8 tensor of the PCM's bytes")
+    have = [(c.numel() if hasattr(c, "numel") else memoryview(c).nbytes) // step for c in clips]
+    k = [(h - n_eff) // cut + 1 if h >= n_eff else 0 for h in have]
+    t = [h - kj * cut for h, kj in zip(have, k)]
+    carry = n_eff - cut
+    need = []
+    for i, (kj, tj) in enumerate(zip(k, t)):                   # Encoder.inner's bookkeeping
+        res.frames[i] = kj + (1 if tj else 0)
+        res.samples[i] = (kj * n_eff - (kj - 1) * carry if kj else 0) + (tj - (carry if kj else 0) if tj else 0)
+        rows = compact.get_samples_min_ge(tj) if (tj and is_compact) else tj
+        need.append((kj * n_eff + rows) * step)
+
+    def alone(i):
+        e = fresh()
+        pcm = _host_bytes(clips[i])
+        res.streams[i] = e.process(pcm).buf + e.flush().buf
+        res.fallback.append(i)
+
+    def run(chunk):
+        while chunk:
+            streams, deeper = _encode_chunk(enc, *([x[i] for i in chunk] for x in (clips, have, k, t)), n_eff, cut, pad_tails, untouched)
+            if not deeper:
+                for i, s in zip(chunk, streams):
+                    res.streams[i] = s
+                return
+            for d in deeper:                                   # the frame-by-frame route of the Encoder decides their depths
+                alone(chunk[d])
+            chunk = [i for d, i in enumerate(chunk) if d not in set(deeper)]
+
+    chunk, size = [], 0
+    for i in range(len(clips)):
+        if chunk and size + need[i] > max_batch_bytes:
+            run(chunk)
+            chunk, size = [], 0
+        chunk.append(i)
+        size += need[i]
+    run(chunk)
+    res.fallback.sort()
     return res

@@ -15,6 +15,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
   * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
     ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
+  * encode_batch: the Encoder's methods, called once per group of frames (``lossless_encode_stream`` is not optional here); optional ``clips_join`` + ``clips_frame_cut`` (the
+    clips stay on the device and one launch cuts every frame; without them the cut is numpy slicing in batch.py).
   * Repairer: ``scan_lib``, ``rs_repair``, ``rs_encode``.
 ``p1_encode`` and ``p1_decode`` move the bare integers (tests and tools)."""
 from __future__ import annotations
@@ -40,8 +42,11 @@ class HipBridge:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
     def _up(self, data: bytes):
-        """host bytes -> device uint8 tensor, straight from the caller's (read-only) buffer"""
+        """host bytes -> device uint8 tensor, straight from the caller's (read-only) buffer; a device tensor (the frame block
+        of encode_batch) is taken as it is"""
         import warnings
+        if isinstance(data, self.torch.Tensor):
+            return data
         if not len(data):
             return self.torch.empty(0, dtype=self.torch.uint8, device=self.device)
         with warnings.catch_warnings():
@@ -87,6 +92,7 @@ class HipBridge:
             bits = 16
         nb = core.payload_bytes(N, C, bits)
         plen = nb if ecc_ratio is None else core.rs_protected_bytes(nb, *ecc_ratio)
+        self.last_escalated = []                              # on None: the frames that need a deeper format (encode_batch reads it)
         if n_frames == 0 or plen >= 0xFFFFFFFF:
             return None
         stream = t.empty((n_frames, 32 + plen), dtype=t.uint8, device=self.device)
@@ -94,6 +100,7 @@ class HipBridge:
         enc = core.analogue_batch(profile, self._up(pcm), fmt, n_frames, N, C, bits, little_endian,
                                   raw_be_ints=raw_be_ints, out=None if ecc_ratio else pay)
         if enc.escalated:
+            self.last_escalated = sorted(enc.escalated)
             return None
         if ecc_ratio is not None:
             core.rs_encode_frames(enc.payload, nb, *ecc_ratio, out=pay)
@@ -301,6 +308,21 @@ class HipBridge:
         if not out.numel():
             return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
         return self._down_pcm(out, out_format, (-1, C)), out_off
+
+    # ------------------------------------------------------------------ encode_batch: the clips' PCM, and their frames cut out
+    def clips_join(self, clips: list, nbytes: list):
+        """The first ``nbytes[j]`` bytes of every clip back to back in one device uint8 tensor: host clips (bytes-like) are
+        joined and uploaded in one copy, device tensors (1-D uint8) are never copied to the host."""
+        t = self.torch
+        if not any(isinstance(c, t.Tensor) for c in clips):
+            return self._up(b"".join(memoryview(c).cast("B")[:n] for c, n in zip(clips, nbytes)))
+        parts = [c[:n].to(self.device) if isinstance(c, t.Tensor) else self._up(bytes(memoryview(c).cast("B")[:n])) for c, n in zip(clips, nbytes) if n]
+        return t.cat(parts) if len(parts) > 1 else parts[0] if parts else t.empty(0, dtype=t.uint8, device=self.device)
+
+    def clips_frame_cut(self, src, row_src, row_valid, row_len: int, step: int):
+        """core.clips_frame_cut: fixed-length frame rows out of the joined clips, one launch -> device uint8 [rows, row_len * step],
+        which the encode methods above take in place of host bytes"""
+        return self.core.clips_frame_cut(src, row_src, row_valid, row_len, step)
 
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch

@@ -681,6 +681,43 @@ def clips_overlap_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, 
     return out, out_off
 
 
+def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: int) -> torch.Tensor:
+    """The Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one launch (frad_clips_frame_cut).
+
+    ``src`` uint8 [bytes]: the clips' raw interleaved PCM back to back, ``step`` = itemsize * channels bytes per sample-frame.
+    Row r of the result is ``row_valid[r]`` sample-frames from sample-frame ``row_src[r]`` of ``src`` on, then zero bytes up to
+    ``row_len`` sample-frames (``row_src`` / ``row_valid``: host integers, one per row; rows may overlap).  Returns uint8
+    [n_rows, row_len * step], the contiguous block the ``*_analogue_batch`` operators read with ``frame_stride = row_len``.
+    The two tables are checked here, on the host, before anything is uploaded or launched."""
+    rs = np.ascontiguousarray(row_src, np.int64).reshape(-1)
+    rv = np.ascontiguousarray(row_valid, np.int32).reshape(-1)
+    if row_len < 1 or step < 1:
+        raise ValueError(f"bad geometry: row_len={row_len} step={step}")
+    if rs.size != rv.size:
+        raise ValueError("row_src and row_valid need one entry per row")
+    _require_cuda(src, "src")
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError(f"src must be a 1-D uint8 tensor (got {src.dtype} {list(src.shape)})")
+    n_rows = rs.size
+    _require_frame_count(n_rows, "rows")
+    have = src.numel() // step
+    if ((rv < 0) | (rv > row_len)).any():
+        raise ValueError(f"row_valid must lie in [0, {row_len}]")
+    if ((rs < 0) | (rs > have - rv.astype(np.int64))).any():                    # (not rs + rv > have: that sum can wrap)
+        raise ValueError(f"a row reads outside src ({have} sample-frames)")
+    out = torch.empty((n_rows, row_len * step), dtype=torch.uint8, device=src.device)
+    if n_rows == 0:
+        return out
+    table = np.empty(12 * n_rows, np.uint8)                    # int64 row_src | int32 row_valid: one upload
+    table[:8 * n_rows] = rs.view(np.uint8)
+    table[8 * n_rows:] = rv.view(np.uint8)
+    dev = torch.from_numpy(table).to(src.device)
+    base = src.data_ptr() if src.numel() else out.data_ptr()   # (every row all padding: nothing is read)
+    with torch.cuda.device(src.device):
+        _lib.load().clips_frame_cut(base, dev.data_ptr(), dev.data_ptr() + 8 * n_rows, n_rows, row_len, step, out.data_ptr(), _stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # raw DEFLATE inflate (frad_inflate_raw): the zlib.decompress(frad, wbits=-15) of profile1.py:59 / profile2.py:61-64
 # ---------------------------------------------------------------------------------------------

@@ -8,6 +8,9 @@
 //                     bits of the 32-bit conversion, 32-bit unsigned the low half of the 64-bit one, an overflowing
 //                     conversion yields the "integer indefinite" 0x80..0 (NaN too).
 //   k_from_f64        float64 [n] -> any of the 20 PCM formats; fused into the profile-4 unpack (k_p4_unpack_pcm).
+//   k_clips_ola       Decoder.overlap + flush() for many clips in one launch, ragged output (frad_clips_overlap_add).
+//   k_clips_cut       the Encoder's frame cut for many clips in one launch: fixed-length rows gathered from one buffer
+//                     (frad_clips_frame_cut).
 //   frad_asfh_scan    host code: walks a FrAD byte stream once and fills a table of frames (tools/asfh.py:98-134,
 //                     decoder.py:82-106) so that the Python decoder no longer parses headers frame by frame.
 #include <atomic>
@@ -243,6 +246,72 @@ __global__ void __launch_bounds__(256) k_clips_ola(const double* __restrict__ fr
     }
 }
 
+// frad_clips_frame_cut: frad_clips_overlap_add turned round -- the encoder's frame cut for many clips, a streaming pass over
+// the fixed-length output rows.  A block owns a tile of CUT_K * 256 chunks of 16 output bytes, a lane every 256th of them; the
+// chunks sit at 16-byte aligned ADDRESSES (chunk c covers output bytes [16 c - head, 16 c - head + 16), head = out mod 16), so
+// that only the first and the last chunk of the whole output can be partial.  A chunk finds its row by one division of its
+// byte offset by the row's byte length -- no search, no scratch, and rows of a few bytes share a lane instead of taking a
+// block each.  A chunk that lies inside one row, and there wholly inside the valid bytes or wholly inside the padding, is one
+// 16-byte load from wherever the source row starts (global memory takes the unaligned address) or none, and one 16-byte
+// store; a chunk that straddles rows, or the end of a row's valid bytes, is put together byte by byte in registers and still
+// leaves as one store.  Only the two partial chunks store bytes.  The stores are plain, not nontemporal: the transform that
+// follows reads the block at once, and a plain store leaves the line in L2.
+constexpr int CUT_K = 4;
+__device__ __forceinline__ v4u load16_anywhere(const unsigned char* p) {
+    v4u q;
+    __builtin_memcpy(&q, p, 16);
+    return q;
+}
+__global__ void __launch_bounds__(256) k_clips_cut(const unsigned char* __restrict__ src, const int64_t* __restrict__ row_src,
+                                                   const int32_t* __restrict__ row_valid, long long n_rows, long long rb, int step,
+                                                   unsigned char* __restrict__ out) {
+    const long long total = n_rows * rb;
+    const long long head = (long long)(reinterpret_cast<uintptr_t>(out) & 15);
+    const long long n_chunks = (total + head + 15) >> 4;
+    const bool small = total + 16 <= 0xffffffffLL;
+    const long long tile = 256LL * CUT_K;
+    for (long long c0 = (long long)blockIdx.x * tile; c0 < n_chunks; c0 += (long long)gridDim.x * tile) {
+#pragma unroll 1
+        for (int it = 0; it < CUT_K; ++it) {                   // (not unrolled: the branches below keep the steps apart anyway)
+            const long long c = c0 + (long long)it * 256 + threadIdx.x;
+            if (c >= n_chunks) break;
+            const long long o = 16 * c - head;                 // < 0 only for chunk 0 of a misaligned output
+            const long long lo = o < 0 ? 0 : o, hi = o + 16 > total ? total : o + 16;
+            long long r = small ? (long long)((uint32_t)lo / (uint32_t)rb) : lo / rb;
+            long long w = lo - r * rb;                         // the chunk's first byte inside row r
+            long long vb = (long long)row_valid[r] * step;     // the row's valid bytes, never more than the row
+            vb = vb < 0 ? 0 : (vb > rb ? rb : vb);
+            const unsigned char* s = src + row_src[r] * step;
+            v4u q = {0, 0, 0, 0};
+            if (hi - lo == 16 && w + 16 <= rb && (w + 16 <= vb || w >= vb)) {
+                if (w < vb) q = load16_anywhere(s + w);
+                *FRAD_GPTR(v4u, out + o) = q;
+                continue;
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const long long b = o + k;
+                if (b < lo || b >= hi) continue;
+                if (w == rb) {                                 // the next row (rb >= 1: at most one step per byte)
+                    ++r; w = 0;
+                    vb = (long long)row_valid[r] * step;
+                    vb = vb < 0 ? 0 : (vb > rb ? rb : vb);
+                    s = src + row_src[r] * step;
+                }
+                const uint32_t x = w < vb ? s[w] : 0u;
+                q[k >> 2] |= x << (8 * (k & 3));
+                ++w;
+            }
+            if (hi - lo == 16) *FRAD_GPTR(v4u, out + o) = q;
+            else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (o + k >= lo && o + k < hi) out[o + k] = (unsigned char)(q[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+    }
+}
+
 template <int SRC>
 int launch_from_f64(int dtype, const unsigned char* in, unsigned char* out, long long n, const Geom& g, hipStream_t s) {
     const int kind = dtype >> 3, lg = (dtype >> 1) & 3, be = dtype & 1;
@@ -407,6 +476,22 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
         default: return FRAD_E_INVALID;
     }
 #undef GO
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+int frad_clips_frame_cut(const void* src, const int64_t* row_src, const int32_t* row_valid, int64_t n_rows, int32_t row_len, int32_t step,
+                         void* out, void* stream) {
+    if (step < 1 || row_len < 1 || n_rows < 0) return FRAD_E_INVALID;
+    if (n_rows == 0) return FRAD_OK;
+    const long long rb = (long long)row_len * step;
+    if (!src || !row_src || !row_valid || !out || n_rows > (0x7fffffffffffffffLL - 32) / rb) return FRAD_E_INVALID;
+    const long long chunks = (n_rows * rb + 30) / 16, per_block = 256LL * CUT_K;       // (an upper bound: head <= 15)
+    long long blocks = (chunks + per_block - 1) / per_block;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_clips_cut, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const unsigned char*>(src), row_src, row_valid, (long long)n_rows, rb, (int)step,
+                       static_cast<unsigned char*>(out));
     FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

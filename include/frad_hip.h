@@ -371,6 +371,21 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
                            const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
                            int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off, int64_t out_rows, void* stream);
 
+/* frad_clips_frame_cut == the Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one pass: fixed-length
+ * rows gathered from arbitrary sample-frame offsets of ONE buffer that holds all clips back to back (all arrays in device
+ * memory).  With rb = row_len * step bytes per row,
+ *   out[r * rb, (r + 1) * rb) = src[row_src[r] * step, (row_src[r] + row_valid[r]) * step), then zero bytes up to rb
+ *   src         raw interleaved PCM, any alignment; step = itemsize * channels bytes per sample-frame (1 = u8 mono, upwards)
+ *   row_src     int64 [n_rows]: the row's first sample-frame in src; rows may overlap (the hop of an overlapped encode)
+ *   row_valid   int32 [n_rows]: 0 .. row_len sample-frames taken from src (0: the row is all padding, row_src is not read from)
+ *   out         [n_rows, row_len] sample-frames, contiguous, any alignment: the block frad_p{0,1,2,4}_analogue read with
+ *               frame_stride = row_len.  Nothing outside its n_rows * rb bytes is written.
+ * One read and one write of the PCM, no scratch; the transform kernels' addressing stays as it is.
+ * The offsets are the caller's to check (core.clips_frame_cut does): every row_src[r] + row_valid[r] must end inside src.
+ * FRAD_E_INVALID for step < 1, row_len < 1, n_rows < 0 and, with rows to write, a null pointer.                          */
+int frad_clips_frame_cut(const void* src, const int64_t* row_src, const int32_t* row_valid, int64_t n_rows, int32_t row_len, int32_t step,
+                         void* out, void* stream);
+
 /* frad_asfh_scan: HOST code (no device involved).  One pass over a FrAD byte stream from `start`: resynchronises on
  * FRM_SIGN and parses every header as ASFH.read does (tools/asfh.py:98-134; the search as decoder.py:82-90), filling
  * frames[0 .. return value).  Stops at the first header or payload that is not completely inside the buffer, at
