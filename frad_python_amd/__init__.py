@@ -13,5 +13,7 @@ from .encoder import Encoder, EncodeResult  # noqa: F401
 from .decoder import Decoder, DecodeResult  # noqa: F401
 from .repairer import Repairer  # noqa: F401
 from .batch import decode_batch, BatchResult, encode_batch, EncodeBatchResult  # noqa: F401
+from .window import StreamIndex, WindowResult, decode_windows  # noqa: F401
 
-__all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "encode_batch", "EncodeBatchResult", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]
+__all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "encode_batch", "EncodeBatchResult",
+           "StreamIndex", "WindowResult", "decode_windows", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]

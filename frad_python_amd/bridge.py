@@ -11,7 +11,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
     ``overlap_add``; ``rs_repair`` for fix_error=True.  Optional, probed with ``getattr``: ``scan_lib`` (the native header
     scanner; without it the byte-wise parser runs and decode_batch goes stream by stream), ``lossless_decode_strided``,
     ``p1_decode_run`` / ``p2_decode_run`` (the fused run), ``compact_decode`` (HipBridge only: device inflate, and frames
-    that stay on the device for decode_batch), ``clips_overlap_add``, ``torch`` + ``device`` (as_tensor).
+    that stay on the device for decode_batch), ``clips_overlap_add``, ``clips_window_add`` (StreamIndex.decode; without it the
+    windows are assembled in numpy), ``torch`` + ``device`` (as_tensor).
   * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
     ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
@@ -304,6 +305,24 @@ class HipBridge:
         flat = None if not tails else tails[0] if len(tails) == 1 else t.cat(tails)
         out, out_off = self.core.clips_overlap_add(frames, clip_frame0, N, C, ratio, flat, tail_off, tail_rows, out_format, tail_win)
         if as_tensor:
+            return out, out_off
+        if not out.numel():
+            return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
+        return self._down_pcm(out, out_format, (-1, C)), out_off
+
+    def clips_window_add(self, frames, clip_f0, clip_m, N, C, ratio, tails: list, tail_off, tail_rows, skip, valid, out_format=None,
+                         tail_win=None, span=None, dst_row=None, out=None, as_tensor=False):
+        """Sample windows of the clips in one launch (core.clips_window_add); ``frames`` and ``tails`` as ``clips_overlap_add``
+        takes them.  Without ``dst_row`` -> (out, out_off) as ``clips_overlap_add`` returns them; with it the spans are written
+        into ``out``, a device tensor that is returned as it is (the caller downloads the batch once)."""
+        t = self.torch
+        dev = lambda a: a if isinstance(a, t.Tensor) else t.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
+        frames = dev(frames) if frames is not None else None
+        tails = [dev(x).reshape(-1) for x in tails]
+        flat = None if not tails else tails[0] if len(tails) == 1 else t.cat(tails)
+        out, out_off = self.core.clips_window_add(frames, clip_f0, clip_m, N, C, ratio, flat, tail_off, tail_rows, skip, valid, out_format,
+                                                  tail_win, span, dst_row, out)
+        if as_tensor or dst_row is not None:
             return out, out_off
         if not out.numel():
             return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off

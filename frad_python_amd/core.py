@@ -681,6 +681,115 @@ def clips_overlap_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, 
     return out, out_off
 
 
+def clips_window_add(frames: torch.Tensor | None, clip_f0, clip_m, N: int, C: int, overlap_ratio: int, tails: torch.Tensor | None = None,
+                     tail_off=None, tail_rows=None, skip=None, valid=None, out_format: str | None = None, tail_win=None, span=None,
+                     dst_row=None, out: torch.Tensor | None = None):
+    """Rows ``[skip[j], skip[j] + valid[j])`` of the timeline ``clips_overlap_add`` writes for clip j, for many clips in one launch
+    (frad_clips_window_add); bit for bit the slice of its output.
+
+    ``frames`` float64 [n_frames, N, C]; clip j is frames ``clip_f0[j] : clip_f0[j] + clip_m[j]`` and the last frame
+    ``tail_rows[j]`` rows at element ``tail_off[j]`` of ``tails`` -- clips may share frames and tails.  ``skip`` defaults to 0,
+    ``valid`` to the rest of the timeline.  Clip j's span is ``span[j]`` sample-frames (default ``valid[j]``), its rows from
+    ``valid[j]`` on are ``out_format``'s silence.  Without ``dst_row`` the spans follow each other in a fresh ``out``; with
+    ``dst_row`` (and ``out``, a contiguous device tensor of float64 or of ``out_format``'s bytes) span j starts at sample-frame
+    ``dst_row[j]`` of ``out`` and nothing else of ``out`` is written.  Returns ``(out, out_off)``, span j at rows
+    ``out_off[j]:out_off[j+1]`` of a fresh ``out``.  Every table is checked here, on the host, before anything is launched."""
+    f0 = np.ascontiguousarray(clip_f0, np.int64).reshape(-1)
+    m = np.ascontiguousarray(clip_m, np.int32).reshape(-1)
+    n_clips = f0.size
+    if N < 1 or C < 1 or not (overlap_ratio == 0 or 2 <= overlap_ratio <= 256):
+        raise ValueError(f"bad geometry: N={N} C={C} overlap_ratio={overlap_ratio}")
+    tr = np.zeros(n_clips, np.int32) if tail_rows is None else np.ascontiguousarray(tail_rows, np.int32).reshape(-1)
+    to = np.zeros(n_clips, np.int64) if tail_off is None else np.ascontiguousarray(tail_off, np.int64).reshape(-1)
+    sk = np.zeros(n_clips, np.int64) if skip is None else np.ascontiguousarray(skip, np.int64).reshape(-1)
+    if m.size != n_clips or tr.size != n_clips or to.size != n_clips or sk.size != n_clips:
+        raise ValueError("clip_m, tail_off, tail_rows and skip need one entry per clip")
+    cut = N * (overlap_ratio - 1) // overlap_ratio if overlap_ratio else N
+    L = N - cut
+    used = m > 0
+    if (m < 0).any() or (f0[used] < 0).any():
+        raise ValueError("clip_f0 and clip_m must not be negative")
+    if used.any():
+        if frames is None:
+            raise ValueError("frames is missing")
+        _require_cuda(frames, "frames")
+        if frames.dtype != torch.float64 or frames.numel() % (N * C):
+            raise ValueError(f"frames must be float64 [n, {N}, {C}]")
+        if (f0[used] > frames.numel() // (N * C) - m[used].astype(np.int64)).any():
+            raise ValueError("a clip's frames lie outside frames")
+    if ((tr < 0) | ((tr > 0) & (tr < L))).any():
+        raise ValueError(f"a last frame needs at least L = {L} rows")
+    has = tr > 0
+    if has.any():
+        if tails is None:
+            raise ValueError("tails is missing")
+        _require_cuda(tails, "tails")
+        if tails.dtype != torch.float64:
+            raise TypeError("tails must be float64")
+        if (to[has] < 0).any() or (to[has] > tails.numel() - tr[has].astype(np.int64) * C).any():
+            raise ValueError("a last frame lies outside tails")
+    timeline = m.astype(np.int64) * cut + np.where(has, tr.astype(np.int64), np.where(used, L, 0))
+    if (sk < 0).any() or (sk > timeline).any():
+        raise ValueError("skip lies outside the clip's timeline")
+    va = (timeline - sk).astype(np.int32) if valid is None else np.ascontiguousarray(valid, np.int32).reshape(-1)
+    if va.size != n_clips or (va < 0).any() or (va.astype(np.int64) > timeline - sk).any():
+        raise ValueError("skip + valid must end inside the clip's timeline")
+    sp = va.astype(np.int64) if span is None else np.ascontiguousarray(span, np.int64).reshape(-1)
+    if sp.size != n_clips or (sp < va).any():
+        raise ValueError("a span must hold its clip's valid rows")
+    out_off = np.zeros(n_clips + 1, np.int64)
+    np.cumsum(sp, out=out_off[1:])
+    total = int(out_off[-1])
+    win = None
+    if tail_win is not None and L:
+        win = np.ascontiguousarray(tail_win, np.float64).reshape(-1)
+        if win.size != L:
+            raise ValueError(f"tail_win must hold L = {L} weights")
+    code = pcm_dtype_code(out_format) if out_format is not None else pcm_dtype_code("f64le")
+    device = frames.device if frames is not None else (tails.device if tails is not None else out.device if out is not None
+                                                       else torch.device("cuda", torch.cuda.current_device()))
+    dst = None
+    if dst_row is None:
+        if out is not None:
+            raise ValueError("out goes with dst_row")
+        out = torch.empty((total, C), dtype=torch.float64, device=device) if out_format is None else \
+            _pcm_out_tensor(out_format, (total, C), device, slack=16)
+    else:
+        dst = np.ascontiguousarray(dst_row, np.int64).reshape(-1)
+        if out is None or dst.size != n_clips:
+            raise ValueError("dst_row needs out and one entry per clip")
+        _require_cuda(out, "out")
+        if out.dtype != (torch.float64 if out_format is None else torch.uint8):
+            raise TypeError("out must be float64, or with out_format the uint8 bytes of that format")
+        have = out.numel() * out.element_size() // (C * itemsize_of(code))
+        if (dst < 0).any() or (dst > have - sp).any():
+            raise ValueError(f"a span lies outside out ({have} sample-frames)")
+        order = np.argsort(dst, kind="stable")
+        order = order[sp[order] > 0]
+        if (dst[order][:-1] + sp[order][:-1] > dst[order][1:]).any():
+            raise ValueError("the spans overlap")
+    if total == 0 or n_clips == 0:
+        return out, out_off
+    _require_frame_count(n_clips, "clips")
+    # every table (and the window) in one upload: int64 clip_f0 | out_off | tail_off | skip | dst_row, float64 window, int32 clip_m | tail_rows | valid
+    wide = [f0, out_off, to, sk] + ([dst] if dst is not None else []) + ([win] if win is not None else [])
+    table = np.concatenate([a.view(np.uint8) for a in wide + [m, tr, va]])
+    dev = torch.from_numpy(table).to(device)
+    p, at, ptr = dev.data_ptr(), 0, []
+    for a in wide + [m, tr, va]:
+        ptr.append(p + at)
+        at += a.nbytes
+    p_f0, p_off, p_to, p_sk = ptr[:4]
+    p_dst = ptr[4] if dst is not None else 0
+    p_win = ptr[len(wide) - 1] if win is not None else 0
+    p_m, p_tr, p_va = ptr[-3:]
+    with torch.cuda.device(device):
+        _lib.load().clips_window_add(frames.data_ptr() if frames is not None else 0, p_f0, p_m, n_clips, N, C, overlap_ratio,
+                                     tails.data_ptr() if tails is not None else 0, p_to, p_tr, p_win, p_sk, p_va, p_dst, code,
+                                     _lib.FRAD_RAW_BE_INTS, out.data_ptr(), p_off, total, _stream_ptr())
+    return out, out_off
+
+
 def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: int) -> torch.Tensor:
     """The Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one launch (frad_clips_frame_cut).
 

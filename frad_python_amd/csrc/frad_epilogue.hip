@@ -9,6 +9,8 @@
 //                     conversion yields the "integer indefinite" 0x80..0 (NaN too).
 //   k_from_f64        float64 [n] -> any of the 20 PCM formats; fused into the profile-4 unpack (k_p4_unpack_pcm).
 //   k_clips_ola       Decoder.overlap + flush() for many clips in one launch, ragged output (frad_clips_overlap_add).
+//   k_clips_win       k_clips_ola on a row range of every clip, zero-padded and scattered into a dense batch
+//                     (frad_clips_window_add: sample windows, window.py).
 //   k_clips_cut       the Encoder's frame cut for many clips in one launch: fixed-length rows gathered from one buffer
 //                     (frad_clips_frame_cut).
 //   frad_asfh_scan    host code: walks a FrAD byte stream once and fills a table of frames (tools/asfh.py:98-134,
@@ -246,6 +248,105 @@ __global__ void __launch_bounds__(256) k_clips_ola(const double* __restrict__ fr
     }
 }
 
+// frad_clips_window_add: k_clips_ola's pass, evaluated on rows [skip, skip + valid) of every clip's timeline and written to a
+// span that may lie anywhere in `out`.  The launch is partitioned by out_off exactly as above (a lane owns 16-byte stores of the
+// partition, searches out_off only when a store has left the clip, one clips_ola_row per row), and the row's sources and
+// weights are clips_ola_row's at timeline row skip + r, so a window is bit for bit the slice of the whole clip.  Rows from
+// `valid` to the end of the span are the conversion of 0.0.  With dst_row the span of clip j starts at sample-frame dst_row[j]
+// of `out` instead of out_off[j], so the address of a store is the clip's: whether it leaves as 16 bytes is decided per store,
+// from that address and from the store lying inside one span (without dst_row the spans follow each other and a store may
+// straddle two, as above); every other store goes element by element, and nothing outside the spans is written.
+struct WinCur : ClipCur {
+    long long skip, shift;                                     // shift: the span's first sample-frame in `out` less out_off[j]
+    int valid;
+};
+template <int LGS> __device__ __forceinline__ v4u pack16(const u64* b) {
+    v4u q = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < (16 >> LGS); ++e) {
+        if constexpr (LGS == 3) { q[2 * e] = (uint32_t)b[e]; q[2 * e + 1] = (uint32_t)(b[e] >> 32); }
+        else if constexpr (LGS == 2) q[e] = (uint32_t)b[e];
+        else if constexpr (LGS == 1) q[e >> 1] |= (uint32_t)b[e] << (16 * (e & 1));
+        else q[e >> 2] |= (uint32_t)b[e] << (8 * (e & 3));
+    }
+    return q;
+}
+struct WinTables {                                             // the per-clip tables of frad_clips_window_add (device memory)
+    const int64_t* clip_f0; const int32_t* clip_m; const int64_t* tail_off; const int32_t* tail_rows;
+    const int64_t* skip; const int32_t* valid; const int64_t* dst_row; const int64_t* out_off;
+};
+template <int KIND, int LGS>
+__global__ void __launch_bounds__(256) k_clips_win(const double* __restrict__ frames, WinTables t, long long n_clips, int N, int C, int cut,
+                                                   int ratio, const double* __restrict__ tails, const double* __restrict__ tail_win,
+                                                   unsigned char* __restrict__ out, long long out_rows, int be, int raw_be) {
+    constexpr int EPT = 16 >> LGS;
+    long long last = t.out_off[n_clips];
+    if (last > out_rows) last = out_rows;                      // never beyond what the caller sized
+    const long long n = last * C, n0 = (long long)t.out_off[0] * C;
+    const long long tile = 256LL * EPT * CLIPS_K;
+    auto enter = [&](WinCur& k, long long j) {
+        k.j = j; k.base = t.out_off[j]; k.end = t.out_off[j + 1];
+        k.f0 = t.clip_f0[j]; k.m = t.clip_m[j]; k.rows = t.tail_rows[j]; k.toff = t.tail_off[j];
+        k.skip = t.skip[j]; k.valid = t.valid[j];
+        k.shift = t.dst_row != nullptr ? (long long)t.dst_row[j] - k.base : 0;
+    };
+    for (long long t0 = (long long)blockIdx.x * tile; t0 < n; t0 += (long long)gridDim.x * tile) {
+        WinCur k;
+        k.j = -1; k.end = 0;
+        for (int it = 0; it < CLIPS_K; ++it) {
+            const long long i0 = t0 + ((long long)it * 256 + threadIdx.x) * EPT;
+            if (i0 >= n) break;
+            long long s;
+            if (n <= 0x7fffffffLL) s = (uint32_t)i0 / (uint32_t)C; else s = i0 / C;
+            int c = (int)(i0 - s * C);
+            if (k.j < 0 || s >= k.end) {                       // the last clip that starts at or before sample-frame s
+                long long lo = k.j < 0 ? 0 : k.j, hi = n_clips;
+                while (hi - lo > 1) {
+                    const long long mid = (lo + hi) >> 1;
+                    if ((long long)t.out_off[mid] <= s) lo = mid; else hi = mid;
+                }
+                enter(k, lo);
+            }
+            // one 16-byte store: all of it inside the launch, at an aligned address, and -- where the spans are scattered -- inside
+            // the span of the clip its first sample is in
+            const long long s_last = s + (uint32_t)(c + EPT - 1) / (uint32_t)C;
+            unsigned char* const at = out + ((i0 + k.shift * C) << LGS);
+            const bool vec = i0 >= n0 && i0 + EPT <= n && (t.dst_row == nullptr || s_last < k.end) &&
+                             (reinterpret_cast<uintptr_t>(at) & 15) == 0;
+            ClipRow row;
+            row.src = nullptr; row.prev = nullptr; row.w_in = 1.0; row.w_out = 0.0;
+            bool have = false, pad = false;
+            u64 b[EPT];
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) {
+                const bool live = i0 + e < n && i0 + e >= n0;
+                double x = 0.0;
+                if (live) {
+                    if (!have || c == 0) {
+                        while (s >= k.end && k.j + 1 < n_clips) enter(k, k.j + 1);
+                        const long long r = s - k.base;
+                        pad = r >= k.valid;
+                        if (!pad) row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, k, k.skip + r);
+                        have = true;
+                    }
+                    if (!pad) {
+                        x = row.src[c];
+                        if (row.prev != nullptr) {
+                            x = x * row.w_in;
+                            x = x + row.prev[c] * row.w_out;
+                        }
+                    }
+                }
+                b[e] = from_f64_bits<KIND, LGS>(x, raw_be != 0 && be);
+                if (be) b[e] = swap_elem<LGS>(b[e]);
+                if (!vec && live) store_elem<LGS>(out + ((i0 + e + k.shift * C) << LGS), b[e]);
+                if (++c == C) { c = 0; ++s; }
+            }
+            if (vec) FRAD_NT_STORE(pack16<LGS>(b), FRAD_GPTR(v4u, at));
+        }
+    }
+}
+
 // frad_clips_frame_cut: frad_clips_overlap_add turned round -- the encoder's frame cut for many clips, a streaming pass over
 // the fixed-length output rows.  A block owns a tile of CUT_K * 256 chunks of 16 output bytes, a lane every 256th of them; the
 // chunks sit at 16-byte aligned ADDRESSES (chunk c covers output bytes [16 c - head, 16 c - head + 16), head = out mod 16), so
@@ -469,6 +570,38 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
     unsigned char* o = static_cast<unsigned char*>(out);
 #define GO(K, L) hipLaunchKernelGGL((k_clips_ola<K, L>), grid, blk, 0, s, frames, clip_frame0, (long long)n_clips, N, C, cut, ratio, tails, \
                                     tail_off, tail_rows, tail_win, o, out_off, (long long)out_rows, be, raw)
+    switch (kind * 4 + lg) {
+        case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
+        case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;
+        case 9: GO(2, 1); break; case 10: GO(2, 2); break; case 11: GO(2, 3); break;
+        default: return FRAD_E_INVALID;
+    }
+#undef GO
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const int32_t* clip_m, int64_t n_clips, int32_t N, int32_t C,
+                          int32_t overlap_ratio, const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
+                          const int64_t* skip, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
+                          const int64_t* out_off, int64_t out_rows, void* stream) {
+    if (!valid_pcm_dtype(out_dtype) || n_clips < 0 || out_rows < 0 || N < 1 || C < 1) return FRAD_E_INVALID;
+    if (overlap_ratio != 0 && (overlap_ratio < 2 || overlap_ratio > 256)) return FRAD_E_INVALID;
+    if (n_clips == 0 || out_rows == 0) return FRAD_OK;
+    if (!clip_f0 || !clip_m || !tail_off || !tail_rows || !skip || !valid || !out_off || !out) return FRAD_E_INVALID;
+    const int cut = overlap_ratio ? (int)((long long)N * (overlap_ratio - 1) / overlap_ratio) : N;     // decoder.py:44
+    const int ratio = overlap_ratio ? overlap_ratio : 1;
+    const int kind = out_dtype >> 3, lg = (out_dtype >> 1) & 3, be = out_dtype & 1, raw = (flags & FRAD_RAW_BE_INTS) ? 1 : 0;
+    const long long total = (long long)out_rows * C, per_block = 256LL * (16 >> lg) * CLIPS_K;
+    long long blocks = (total + per_block - 1) / per_block;
+    if (blocks > 16384) blocks = 16384;
+    if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks), blk(256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned char* o = static_cast<unsigned char*>(out);
+    const WinTables t{clip_f0, clip_m, tail_off, tail_rows, skip, valid, dst_row, out_off};
+#define GO(K, L) hipLaunchKernelGGL((k_clips_win<K, L>), grid, blk, 0, s, frames, t, (long long)n_clips, N, C, cut, ratio, tails, tail_win, o, \
+                                    (long long)out_rows, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
         case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;

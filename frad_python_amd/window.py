@@ -1,0 +1,308 @@
+"""``StreamIndex`` and ``decode_windows``: sample windows of many streams decoded in one device pass.
+
+A data loader takes a crop -- a second or two out of a file that is minutes long.  ``decode_batch`` and a slice on the host
+give it, at the cost of the whole stream.  A FrAD stream is a sequence of self-contained frames, the header scan gives every
+frame's place and geometry without the device, and an output sample depends on at most two frames: its own and, inside the
+Hann cross-fade, the one before.  ``StreamIndex`` scans the streams once and keeps the per-stream plan of ``decode_batch``;
+``index.decode`` selects the frames the windows need (merged per stream, so that overlapping windows share what is decoded for
+them), sends the frames of ALL windows of a geometry group through each decode stage in one call, and one launch of
+``frad_clips_window_add`` per group cross-fades, cuts, converts and writes every window -- ragged, or with ``pad_to`` scattered
+into one dense zero-padded ``[B, T, C]`` batch.
+
+Contract: ``res.pcm[k]`` of window ``(i, start, length)`` is bit for bit ``decode_batch([streams[i]], ...).pcm[0][start:start +
+length]`` with the same keywords on the same bridge.  A stream that does not have the batched shape is decoded whole by a
+per-stream ``Decoder``, as ``decode_batch`` does, sliced on the host and listed in ``res.fallback``."""
+from __future__ import annotations
+
+import numpy as np
+
+from .backend.pcmformat import ff_format_to_numpy_type, from_f64
+from .batch import _frames, _plan, _scan_together, clips_overlap_host, decode_batch
+from .frames import repair
+
+
+class WindowResult:
+    """``pcm[k]`` [rows_k, channels] of window k; ``lengths[k]`` = rows_k; ``batch``: with ``pad_to=T`` the dense [B, T, C] block
+    (``pcm[k]`` are then views into it), else None; ``fallback``: the sorted indices of the streams a per-stream ``Decoder``
+    decoded."""
+
+    def __init__(self, n: int):
+        self.pcm = [None] * n
+        self.lengths = [0] * n
+        self.batch = None
+        self.fallback = []
+
+
+def select_frames(a: int, b: int, cut: int, L: int, m: int, has_tail: bool):
+    """The frames rows [a, b), a < b, of a stream's timeline depend on -- m main frames ``cut`` apart that overlap by L rows, then
+    the tail frame or the flush fragment.  -> (fa, fb, tail): main frames [fa, fb) and whether the tail frame is read.  A row
+    reads its own frame and, in that frame's first L rows, the one before."""
+    body = m * cut
+    if a < body:
+        fa = a // cut
+        if fa > 0 and a % cut < L:
+            fa -= 1
+    elif has_tail and (a - body >= L or m == 0):
+        fa = m
+    else:
+        fa = m - 1                                            # the tail's fade, or the flush fragment: rows of the last main frame
+    if b <= body:
+        return fa, (b - 1) // cut + 1, False
+    return fa, m, has_tail
+
+
+def merge_runs(ranges) -> list:
+    """half-open ranges -> the sorted disjoint runs that cover them (ranges that touch are one run)"""
+    runs = []
+    for lo, hi in sorted(r for r in ranges if r[1] > r[0]):
+        if runs and lo <= runs[-1][1]:
+            runs[-1][1] = max(runs[-1][1], hi)
+        else:
+            runs.append([lo, hi])
+    return runs
+
+
+def clips_window_host(frames, clip_f0, clip_m, N, C, ratio, tails: list, tail_off, tail_rows, skip, valid, out_format=None):
+    """What ``frad_clips_window_add`` computes without padding, with ``clips_overlap_host``'s arithmetic: rows ``skip[j] : skip[j] +
+    valid[j]`` of the timeline of clip j (frames ``clip_f0[j] : clip_f0[j] + clip_m[j]``, the tail at ``tail_off[j]``), clip
+    after clip.  For a bridge without ``clips_window_add``, and the kernel tests' model.  -> (ndarray [rows, C], out_off)"""
+    flat = [np.concatenate([np.asarray(t, np.float64).reshape(-1) for t in tails])] if tails else []
+    pieces, out_off = [], [0]
+    for j in range(len(clip_f0)):
+        f0, m = int(clip_f0[j]), int(clip_m[j])
+        whole, _ = clips_overlap_host(frames[f0:f0 + m] if m else None, [0, m], N, C, ratio, flat, [tail_off[j]], [tail_rows[j]])
+        pieces.append(whole[int(skip[j]):int(skip[j]) + int(valid[j])])
+        out_off.append(out_off[-1] + len(pieces[-1]))
+    out = np.concatenate(pieces) if pieces else np.zeros((0, C))
+    if out_format is not None:
+        out = from_f64(out, out_format)
+    return out, np.asarray(out_off, np.int64)
+
+
+class StreamIndex:
+    """The frame index of a set of complete streams: one header scan (``frad_asfh_scan`` over all of them, no device work) and the
+    per-stream plan of ``decode_batch``, kept for any number of ``decode`` calls.  ``fix_error`` belongs to the index: how a
+    protected frame is classified depends on it.
+
+    ``samples[i]``: the rows ``decode_batch`` returns for stream i, from the headers alone -- None for a stream that does not
+    have the batched shape (``fallback`` lists those; what is known of them is known only after decoding).  ``srate[i]``,
+    ``channels[i]`` (of the last header), ``frames[i]``: as ``BatchResult`` gives them, None for a fallback stream."""
+
+    def __init__(self, streams, *, fix_error: bool = False, bridge=None):
+        if bridge is None:
+            from .bridge import HipBridge
+            bridge = HipBridge()
+        self.bridge, self.fix_error = bridge, fix_error
+        self.streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
+        n = len(self.streams)
+        scan_lib = getattr(bridge, "scan_lib", None)
+        if scan_lib is None or not n:
+            self.plans = [None] * n                            # no native scanner behind this bridge: every stream on its own
+        else:
+            joined, rows_of = _scan_together(scan_lib.asfh_scan, self.streams)
+            self.plans = [_plan(rows, joined, fix_error) if rows is not None else None for rows in rows_of]
+        self.samples, self.srate, self.channels, self.frames = ([None] * n for _ in range(4))
+        self.fallback = [i for i, p in enumerate(self.plans) if p is None]
+        for i, p in enumerate(self.plans):
+            if p is not None:
+                self.samples[i] = sum(self._geometry(p)[4:]) if p.key is not None else 0
+                self.srate[i], self.channels[i], self.frames[i] = p.srate, p.channels, p.frames
+
+    @staticmethod
+    def _geometry(p):
+        """-> (cut, L, m, tail rows R, body = m * cut, rows behind the body) of a planned stream with frames"""
+        N, ratio = p.key[1], p.key[6]
+        cut = N * (ratio - 1) // ratio if ratio else N
+        m = len(p.main)
+        R = p.tail_key[1] if p.tail_key is not None else 0
+        return cut, N - cut, m, R, m * cut, R if R else (N - cut if m else 0)
+
+    def decode(self, windows, *, pad_to: int | None = None, out_format: str | None = None, device_inflate: bool = False,
+               as_tensor: bool = False, max_batch_bytes: int = 1 << 30) -> WindowResult:
+        """Decode ``windows``, a sequence of ``(stream, start, length)``: rows ``start : start + length`` of stream ``stream`` of
+        the index (``length`` None: to the end; a window is clipped to the stream's end; a stream may be named any number of
+        times).  ``out_format``, ``device_inflate``, ``as_tensor`` and ``max_batch_bytes`` mean what they mean for
+        ``decode_batch`` (a group is cut into chunks of whole windows).  ``pad_to=T``: ``res.batch`` is the dense block
+        [len(windows), T, C] -- an ndarray of ``out_format``'s dtype (float64 without one), or with ``as_tensor`` a device tensor
+        (float64, or the uint8 bytes [B, T, C * itemsize] of ``out_format``) -- rows past ``res.lengths[k]`` hold the format's
+        silence, and ``res.pcm[k]`` are views into it; ValueError when the streams used differ in channel count or a window is
+        longer than T."""
+        br = self.bridge
+        dt = np.dtype(np.float64) if out_format is None else ff_format_to_numpy_type(out_format)
+        if as_tensor and getattr(br, "torch", None) is None:
+            raise ValueError("as_tensor needs a bridge that keeps tensors on the device")
+        wins = []
+        for i, start, length in windows:
+            if not 0 <= i < len(self.streams):
+                raise IndexError(f"stream {i} is not in the index")
+            if start < 0 or (length is not None and length < 0):
+                raise ValueError(f"a window needs start >= 0 and length >= 0 (got {start}, {length})")
+            wins.append((i, start, length))
+        res = WindowResult(len(wins))
+        kw = dict(fix_error=self.fix_error, out_format=out_format, device_inflate=device_inflate, bridge=br)
+        whole = {i: decode_batch([self.streams[i]], **kw).pcm[0] for i in sorted({w[0] for w in wins if self.plans[w[0]] is None})}
+        res.fallback = sorted(whole)
+        # ---- every window as rows [a, b) of its stream, clipped; the ones a launch writes, by geometry key
+        spans, groups, channels = [], {}, set()
+        for k, (i, start, length) in enumerate(wins):
+            p = self.plans[i]
+            total = len(whole[i]) if p is None else self.samples[i]
+            a = min(start, total)
+            b = total if length is None else max(a, min(start + length, total))
+            spans.append((a, b))
+            res.lengths[k] = b - a
+            channels.add(whole[i].shape[1] if p is None else p.channels)
+            if p is not None and p.key is not None and (b > a or pad_to is not None):
+                groups.setdefault(p.key, []).append(k)
+        on_dev = getattr(br, "clips_window_add", None)
+        dense = None
+        if pad_to is not None:
+            if len(channels) > 1:
+                raise ValueError(f"a dense batch needs one channel count (the streams used have {sorted(channels)})")
+            if any(n > pad_to for n in res.lengths):
+                raise ValueError(f"a window is longer than pad_to = {pad_to}")
+            C = channels.pop() if channels else 0
+            if on_dev is not None:                             # the launches scatter into it; what no launch writes is filled below
+                t = br.torch
+                dense = t.empty((len(wins), pad_to, C), dtype=t.float64, device=br.device) if out_format is None else \
+                    t.empty((len(wins), pad_to, C * dt.itemsize), dtype=t.uint8, device=br.device)
+            else:
+                dense = np.empty((len(wins), pad_to, C), dt)
+
+        def finish(k, pcm):
+            if as_tensor and isinstance(pcm, np.ndarray):
+                t = br.torch
+                raw = np.ascontiguousarray(pcm)
+                pcm = t.from_numpy(raw if out_format is None else raw.view(np.uint8).reshape(-1)).to(br.device)
+            res.pcm[k] = pcm
+
+        launched = set()
+
+        def run(key, chunk, needs_of):
+            self._decode_chunk(key, chunk, wins, spans, needs_of, finish, dense, pad_to, out_format, device_inflate, as_tensor)
+            launched.update(chunk)
+
+        for key, members in groups.items():
+            chunk, needs_of, bytes_of, size = [], {}, {}, 0    # needs_of[i]: the (fa, fb, tail) of stream i's windows in the chunk
+            for k in members:
+                i = wins[k][0]
+                need = self._needs(i, *spans[k])
+                grown = needs_of.get(i, []) + [need]
+                if chunk and size - bytes_of.get(i, 0) + self._bytes(i, grown) > max_batch_bytes:
+                    run(key, chunk, needs_of)
+                    chunk, needs_of, bytes_of, size, grown = [], {}, {}, 0, [need]
+                chunk.append(k)
+                size -= bytes_of.get(i, 0)
+                needs_of[i], bytes_of[i] = grown, self._bytes(i, grown)
+                size += bytes_of[i]
+            run(key, chunk, needs_of)
+        # ---- the windows no launch wrote: a fallback stream's slice, and the empty ones
+        silence = from_f64(np.zeros(1), dt)
+        for k, (i, start, length) in enumerate(wins):
+            if k in launched:
+                continue
+            a, b = spans[k]
+            piece = whole[i][a:b] if self.plans[i] is None else np.zeros((0, self.plans[i].channels), dt)
+            if dense is None:
+                finish(k, piece)
+                continue
+            host = isinstance(dense, np.ndarray)
+            row = dense[k] if host else np.empty((pad_to, C), dt)
+            row[:b - a] = piece
+            row[b - a:] = silence
+            if not host:
+                dense[k] = br.torch.from_numpy(row if out_format is None else row.view(np.uint8)).to(br.device)
+        if dense is not None:
+            if not as_tensor and not isinstance(dense, np.ndarray):
+                dense = dense.cpu().numpy().view(dt)           # one download of the whole batch
+            res.batch = dense
+            for k in range(len(wins)):
+                view = dense[k, :res.lengths[k]]
+                res.pcm[k] = view.reshape(-1) if as_tensor and out_format is not None else view
+        return res
+
+    # ------------------------------------------------------------------------------------------------ what a window needs
+    def _needs(self, i: int, a: int, b: int):
+        """-> (fa, fb, tail) of rows [a, b) of planned stream i; an empty window needs nothing"""
+        if a >= b:
+            return 0, 0, False
+        cut, L, m, R, _, _ = self._geometry(self.plans[i])
+        return select_frames(a, b, cut, L, m, R > 0)
+
+    def _bytes(self, i: int, needs: list) -> int:
+        """float64 bytes of the frames decoded for stream i when its windows need ``needs``: the merged runs, and the tail if read"""
+        p = self.plans[i]
+        N, C = p.key[1], p.key[2]
+        return (sum(hi - lo for lo, hi in merge_runs((fa, fb) for fa, fb, _ in needs)) * N
+                + (p.tail_key[1] if any(t for _, _, t in needs) else 0)) * C * 8
+
+    def _decode_chunk(self, key, chunk, wins, spans, needs_of, finish, dense, pad_to, out_format, device_inflate, as_tensor):
+        """The windows ``chunk`` of one geometry group: every stage once over the merged frame runs of their streams, the tails
+        grouped by their size, then one ``clips_window_add``."""
+        br = self.bridge
+        N, C, ratio = key[1], key[2], key[6]
+        cut = N * (ratio - 1) // ratio if ratio else N
+        main, place, tails_by = [], {}, {}
+        for i, needs in needs_of.items():                      # place[i]: [(lo, hi, the run's first frame in `main`)]
+            p = self.plans[i]
+            place[i] = []
+            for lo, hi in merge_runs((fa, fb) for fa, fb, _ in needs):
+                place[i].append((lo, hi, len(main)))
+                main.extend(p.main[lo:hi])
+            if any(t for _, _, t in needs):
+                tails_by.setdefault(p.tail_key, []).append(i)
+        order = [i for members in tails_by.values() for i in members]
+        fixed = repair(br, main + [self.plans[i].tail for i in order])
+        main, tail_payloads = fixed[:len(main)], fixed[len(main):]
+        frames = _frames(br, key, main, device_inflate) if main else None
+        tails, tail_at, off, at = [], {}, 0, 0
+        for tkey, members in tails_by.items():                 # the last frames, grouped again by their size
+            tails.append(_frames(br, tkey, tail_payloads[at:at + len(members)], device_inflate))
+            at += len(members)
+            for n, i in enumerate(members):
+                tail_at[i] = (off + n * tkey[1] * C, tkey[1])
+            off += len(members) * tkey[1] * C
+        n = len(chunk)
+        clip_f0, clip_m = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        tail_off, tail_rows = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        skip, valid = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        for j, k in enumerate(chunk):
+            i, (a, b) = wins[k][0], spans[k]
+            fa, fb, tail = self._needs(i, a, b)
+            if fb > fa:
+                lo, _, first = next(r for r in place[i] if r[0] <= fa and fb <= r[1])
+                clip_f0[j], clip_m[j] = first + fa - lo, fb - fa
+            if tail:
+                tail_off[j], tail_rows[j] = tail_at[i]
+            if b > a:                                         # (an empty window of a dense batch: a span of silence)
+                skip[j], valid[j] = a - fa * cut, b - a
+        on_dev = getattr(br, "clips_window_add", None)
+        if on_dev is None:
+            out, out_off = clips_window_host(frames, clip_f0, clip_m, N, C, ratio, tails, tail_off, tail_rows, skip, valid, out_format)
+            for j, k in enumerate(chunk):
+                piece = out[int(out_off[j]):int(out_off[j + 1])]
+                if dense is None:
+                    finish(k, piece)
+                else:
+                    dense[k, :len(piece)] = piece
+                    dense[k, len(piece):] = from_f64(np.zeros(1), dense.dtype)
+            return
+        win = None
+        if ratio > 1:
+            L = N - cut
+            win = 0.5 * (1 - np.cos(np.pi * np.arange(1, L + 1) / (L + 1)))       # Decoder._overlap_host's weights
+        if dense is not None:
+            on_dev(frames, clip_f0, clip_m, N, C, ratio, tails, tail_off, tail_rows, skip, valid, out_format, win,
+                   span=np.full(n, pad_to, np.int64), dst_row=np.asarray(chunk, np.int64) * pad_to, out=dense)
+            return
+        out, out_off = on_dev(frames, clip_f0, clip_m, N, C, ratio, tails, tail_off, tail_rows, skip, valid, out_format, win,
+                              as_tensor=as_tensor)
+        step = C * np.dtype(ff_format_to_numpy_type(out_format)).itemsize if as_tensor and out_format is not None else 1
+        for j, k in enumerate(chunk):
+            finish(k, out[int(out_off[j]) * step:int(out_off[j + 1]) * step])
+
+
+def decode_windows(streams, windows, *, fix_error: bool = False, bridge=None, **kw) -> WindowResult:
+    """``StreamIndex(streams, fix_error=fix_error, bridge=bridge).decode(windows, **kw)``: a throw-away index for one call.  A
+    window's stream is its position in ``streams``."""
+    return StreamIndex(streams, fix_error=fix_error, bridge=bridge).decode(windows, **kw)

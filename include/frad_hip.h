@@ -371,6 +371,37 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
                            const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
                            int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off, int64_t out_rows, void* stream);
 
+/* frad_clips_window_add == frad_clips_overlap_add's arithmetic on an arbitrary row range of each clip: sample windows of many
+ * streams in one pass, ragged or scattered into a zero-padded batch (all arrays in device memory).  frames, N, C, overlap_ratio,
+ * tails, tail_off, tail_rows, tail_win, out_dtype, flags and stream are frad_clips_overlap_add's.
+ *   clip_f0     int64 [n_clips], clip_m int32 [n_clips]: clip j's equal-length frames are frames[clip_f0[j] .. clip_f0[j] + clip_m[j])
+ *               (clip_m[j] >= 0).  The ranges of different clips may overlap or coincide, and so may their tail_off: the windows of
+ *               one stream share the frames decoded for it.
+ *   skip        int64 [n_clips]: the first row of clip j's own timeline to produce.  The timeline is the one
+ *               frad_clips_overlap_add writes for a clip of those frames and that tail: row r < m * cut is row r % cut of frame
+ *               r / cut, faded against row cut + r % cut of the frame before when r % cut < L and r / cut > 0; after m * cut rows
+ *               come the tail_rows[j] rows of the tail (its first L rows faded against frame m - 1 when m > 0), or without a tail
+ *               the L rows of the flush fragment (m > 0).  Row for row the values are frad_clips_overlap_add's, bit for bit.
+ *   valid       int32 [n_clips]: the rows produced, 0 <= valid[j] <= out_off[j+1] - out_off[j], and skip[j] + valid[j] must not
+ *               pass the end of the timeline.  The other rows of the clip's span are written as the conversion of 0.0 to out_dtype
+ *               (silence in the output format: 0x80 for FRAD_PCM_U8, not the zero byte).
+ *   out_off     int64 [n_clips + 1], non-decreasing: it partitions the launch, clip j's span is out_off[j+1] - out_off[j]
+ *               sample-frames long.  out_rows == out_off[n_clips] (the host's copy: it sizes the launch; spans beyond
+ *               min(out_rows, out_off[n_clips]) are not written).
+ *   dst_row     int64 [n_clips] or NULL.  NULL: clip j's span starts at sample-frame out_off[j] of out, as in
+ *               frad_clips_overlap_add (sample-frames before out_off[0] are left alone).  Given: the span starts at sample-frame
+ *               dst_row[j] of out and out_off only partitions the launch -- one launch per geometry group scatters into a batch
+ *               whose rows belong to several groups.  The spans must be disjoint; nothing outside them is written.
+ * A span leaves in 16-byte stores where its address allows it (dst_row[j] * C * itemsize a multiple of 16 from an aligned out),
+ * element by element elsewhere.  No scratch memory.
+ * The tables are the caller's to check (core.clips_window_add does).  FRAD_E_INVALID for N, C, the ratio, the dtype, negative
+ * counts and, with rows to write, a null table (dst_row, tail_win, and frames / tails that no clip reads may be NULL); FRAD_OK
+ * without a launch for n_clips == 0 or out_rows == 0.                                                                        */
+int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const int32_t* clip_m, int64_t n_clips, int32_t N, int32_t C,
+                          int32_t overlap_ratio, const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
+                          const int64_t* skip, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
+                          const int64_t* out_off, int64_t out_rows, void* stream);
+
 /* frad_clips_frame_cut == the Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one pass: fixed-length
  * rows gathered from arbitrary sample-frame offsets of ONE buffer that holds all clips back to back (all arrays in device
  * memory).  With rb = row_len * step bytes per row,
