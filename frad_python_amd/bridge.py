@@ -12,7 +12,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
     scanner; without it the byte-wise parser runs and decode_batch goes stream by stream), ``lossless_decode_strided``,
     ``p1_decode_run`` / ``p2_decode_run`` (the fused run), ``compact_decode`` (HipBridge only: device inflate, and frames
     that stay on the device for decode_batch), ``clips_overlap_add``, ``clips_window_add`` (StreamIndex.decode; without it the
-    windows are assembled in numpy), ``torch`` + ``device`` (as_tensor).
+    windows are assembled in numpy), ``clips_resample`` (StreamIndex.decode(srate=); without it ``window.clips_resample_host``
+    resamples in numpy), ``torch`` + ``device`` (as_tensor).
   * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
     ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
@@ -41,6 +42,7 @@ class HipBridge:
         self.torch, self.core = torch, core
         self.scan_lib = core._lib.load()                      # frad_asfh_scan: the decoder's native header scanner
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._resample_taps = {}                              # (up, down) -> the taps on the device (clips_resample)
 
     def _up(self, data: bytes):
         """host bytes -> device uint8 tensor, straight from the caller's (read-only) buffer; a device tensor (the frame block
@@ -322,6 +324,25 @@ class HipBridge:
         flat = None if not tails else tails[0] if len(tails) == 1 else t.cat(tails)
         out, out_off = self.core.clips_window_add(frames, clip_f0, clip_m, N, C, ratio, flat, tail_off, tail_rows, skip, valid, out_format,
                                                   tail_win, span, dst_row, out)
+        if as_tensor or dst_row is not None:
+            return out, out_off
+        if not out.numel():
+            return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
+        return self._down_pcm(out, out_format, (-1, C)), out_off
+
+    def clips_resample(self, src, src_off, src_row0, src_rows, C, up, down, out_row0, valid, out_format=None, span=None, dst_row=None,
+                       out=None, as_tensor=False):
+        """Source spans resampled by ``up / down`` in one launch (core.clips_resample).  ``src``: a flat float64 device tensor or
+        ndarray; the taps of a ratio are computed once and stay on the device.  Results as ``clips_window_add`` returns them."""
+        t = self.torch
+        cache = self._resample_taps
+        if (up, down) not in cache:
+            from .window import resample_taps
+            cache[up, down] = t.from_numpy(resample_taps(up, down).copy()).to(self.device)   # (the cached array is read-only)
+        if src is not None and not isinstance(src, t.Tensor):
+            src = t.from_numpy(np.ascontiguousarray(src, np.float64).reshape(-1)).to(self.device)
+        out, out_off = self.core.clips_resample(src, src_off, src_row0, src_rows, C, up, down, cache[up, down], out_row0, valid, out_format,
+                                                span, dst_row, out)
         if as_tensor or dst_row is not None:
             return out, out_off
         if not out.numel():

@@ -790,6 +790,88 @@ def clips_window_add(frames: torch.Tensor | None, clip_f0, clip_m, N: int, C: in
     return out, out_off
 
 
+def clips_resample(src: torch.Tensor | None, src_off, src_row0, src_rows, C: int, up: int, down: int, taps: torch.Tensor, out_row0,
+                   valid, out_format: str | None = None, span=None, dst_row=None, out: torch.Tensor | None = None):
+    """Polyphase resampling by ``up / down`` of many ragged float64 spans in one launch (frad_clips_resample), converted and
+    written as ``clips_window_add`` writes its windows.
+
+    ``src`` flat float64: clip j's source rows are ``src_rows[j]`` rows of ``C`` at element ``src_off[j]``, rows ``src_row0[j] ..``
+    of the stream's timeline; rows outside count as zero; spans may overlap.  ``taps``: the device copy of
+    ``window.resample_taps(up, down)``.  Rows ``out_row0[j] : out_row0[j] + valid[j]`` of the resampled stream are written to
+    clip j's span of ``span[j]`` sample-frames (default ``valid[j]``), the rest of the span is ``out_format``'s silence; ``dst_row``
+    and ``out`` as for ``clips_window_add``.  Returns ``(out, out_off)``.  Every table is checked here, on the host, before
+    anything is launched."""
+    so = np.ascontiguousarray(src_off, np.int64).reshape(-1)
+    s0 = np.ascontiguousarray(src_row0, np.int64).reshape(-1)
+    sr = np.ascontiguousarray(src_rows, np.int32).reshape(-1)
+    o0 = np.ascontiguousarray(out_row0, np.int64).reshape(-1)
+    va = np.ascontiguousarray(valid, np.int32).reshape(-1)
+    n_clips = so.size
+    if C < 1 or up < 1 or down < 1:
+        raise ValueError(f"bad geometry: C={C} up={up} down={down}")
+    if s0.size != n_clips or sr.size != n_clips or o0.size != n_clips or va.size != n_clips:
+        raise ValueError("src_off, src_row0, src_rows, out_row0 and valid need one entry per clip")
+    half = 10 * max(up, down)
+    _require_cuda(taps, "taps")
+    if taps.dtype != torch.float64 or taps.numel() != 2 * half + 1:
+        raise ValueError(f"taps must be the {2 * half + 1} float64 taps of {up}/{down}")
+    if (sr < 0).any() or (s0 < 0).any() or (o0 < 0).any() or (va < 0).any():
+        raise ValueError("src_row0, src_rows, out_row0 and valid must not be negative")
+    used = sr > 0
+    if used.any():
+        if src is None:
+            raise ValueError("src is missing")
+        _require_cuda(src, "src")
+        if src.dtype != torch.float64:
+            raise TypeError("src must be float64")
+        if (so[used] < 0).any() or (so[used] > src.numel() - sr[used].astype(np.int64) * C).any():
+            raise ValueError("a clip's source rows lie outside src")
+    sp = va.astype(np.int64) if span is None else np.ascontiguousarray(span, np.int64).reshape(-1)
+    if sp.size != n_clips or (sp < va).any():
+        raise ValueError("a span must hold its clip's valid rows")
+    out_off = np.zeros(n_clips + 1, np.int64)
+    np.cumsum(sp, out=out_off[1:])
+    total = int(out_off[-1])
+    code = pcm_dtype_code(out_format) if out_format is not None else pcm_dtype_code("f64le")
+    device = taps.device
+    dst = None
+    if dst_row is None:
+        if out is not None:
+            raise ValueError("out goes with dst_row")
+        out = torch.empty((total, C), dtype=torch.float64, device=device) if out_format is None else \
+            _pcm_out_tensor(out_format, (total, C), device, slack=16)
+    else:
+        dst = np.ascontiguousarray(dst_row, np.int64).reshape(-1)
+        if out is None or dst.size != n_clips:
+            raise ValueError("dst_row needs out and one entry per clip")
+        _require_cuda(out, "out")
+        if out.dtype != (torch.float64 if out_format is None else torch.uint8):
+            raise TypeError("out must be float64, or with out_format the uint8 bytes of that format")
+        have = out.numel() * out.element_size() // (C * itemsize_of(code))
+        if (dst < 0).any() or (dst > have - sp).any():
+            raise ValueError(f"a span lies outside out ({have} sample-frames)")
+        order = np.argsort(dst, kind="stable")
+        order = order[sp[order] > 0]
+        if (dst[order][:-1] + sp[order][:-1] > dst[order][1:]).any():
+            raise ValueError("the spans overlap")
+    if total == 0 or n_clips == 0:
+        return out, out_off
+    _require_frame_count(n_clips, "clips")
+    # every table in one upload: int64 src_off | src_row0 | out_row0 | out_off | dst_row, int32 src_rows | valid
+    wide = [so, s0, o0, out_off] + ([dst] if dst is not None else [])
+    table = np.concatenate([a.view(np.uint8) for a in wide + [sr, va]])
+    dev = torch.from_numpy(table).to(device)
+    p, at, ptr = dev.data_ptr(), 0, []
+    for a in wide + [sr, va]:
+        ptr.append(p + at)
+        at += a.nbytes
+    with torch.cuda.device(device):
+        _lib.load().clips_resample(src.data_ptr() if used.any() else 0, ptr[0], ptr[1], ptr[-2], n_clips, C, up, down, taps.data_ptr(), half,
+                                   ptr[2], ptr[-1], ptr[4] if dst is not None else 0, code, _lib.FRAD_RAW_BE_INTS, out.data_ptr(), ptr[3],
+                                   total, _stream_ptr())
+    return out, out_off
+
+
 def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: int) -> torch.Tensor:
     """The Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one launch (frad_clips_frame_cut).
 

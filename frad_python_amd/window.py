@@ -11,8 +11,15 @@ into one dense zero-padded ``[B, T, C]`` batch.
 
 Contract: ``res.pcm[k]`` of window ``(i, start, length)`` is bit for bit ``decode_batch([streams[i]], ...).pcm[0][start:start +
 length]`` with the same keywords on the same bridge.  A stream that does not have the batched shape is decoded whole by a
-per-stream ``Decoder``, as ``decode_batch`` does, sliced on the host and listed in ``res.fallback``."""
+per-stream ``Decoder``, as ``decode_batch`` does, sliced on the host and listed in ``res.fallback``.
+
+``index.decode(..., srate=R)`` takes the windows from every stream resampled to R Hz: the source rows a window
+reads are decoded as above, to float64 on the device, and one launch of ``frad_clips_resample`` per ratio -- ``scipy.signal.
+resample_poly``'s arithmetic -- resamples, converts and writes them, so that streams of mixed rates give one dense batch."""
 from __future__ import annotations
+
+import functools
+import math
 
 import numpy as np
 
@@ -79,6 +86,77 @@ def clips_window_host(frames, clip_f0, clip_m, N, C, ratio, tails: list, tail_of
     return out, np.asarray(out_off, np.int64)
 
 
+RESAMPLE_MAX = 2048                                            # max(up, down) of StreamIndex.decode(srate=): beyond it the taps are no table
+
+
+def resample_ratio(srate_out: int, srate_in: int):
+    """-> (up, down, half) of resampling ``srate_in`` to ``srate_out``: the reduced ratio, and the taps' half length 10 * max"""
+    g = math.gcd(srate_out, srate_in)
+    up, down = srate_out // g, srate_in // g
+    return up, down, 10 * max(up, down)
+
+
+@functools.lru_cache(maxsize=None)
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """The 2 * half + 1 taps of ``scipy.signal.resample_poly(x, up, down)`` with default arguments, in float64 with numpy alone:
+    firwin(2 * half + 1, 1 / M, window=("kaiser", 5.0)) * up, M = max(up, down), half = 10 * M.  Read-only (it is cached)."""
+    M = max(up, down)
+    half = 10 * M
+    h = np.sinc((np.arange(2 * half + 1) - half) / M) / M * np.kaiser(2 * half + 1, 5.0)
+    h = h / h.sum() * up
+    h.setflags(write=False)
+    return h
+
+
+def resample_rows(n_in: int, up: int, down: int) -> int:
+    """rows of ``n_in`` rows resampled by up / down: ceil(n_in * up / down)"""
+    return -(-n_in * up // down)
+
+
+def resample_needs(a: int, b: int, up: int, down: int, n_in: int):
+    """-> the source rows [lo, hi) that output rows [a, b) of the resampled stream read, clipped to the stream's ``n_in`` rows"""
+    if a >= b:
+        return 0, 0
+    half = 10 * max(up, down)
+    lo = max(0, -(-(a * down - half) // up))
+    hi = min(n_in, ((b - 1) * down + half) // up + 1)
+    return (lo, hi) if hi > lo else (0, 0)
+
+
+def clips_resample_host(src, src_off, src_row0, src_rows, C, up, down, out_row0, valid, out_format=None):
+    """What ``frad_clips_resample`` computes without padding, in numpy: rows ``out_row0[j] : out_row0[j] + valid[j]`` of the
+    stream resampled by ``up / down``, from the ``src_rows[j]`` source rows at element ``src_off[j]`` of the flat float64 ``src``
+    that are rows ``src_row0[j] ..`` of the stream (rows outside count as zero), clip after clip.  The definition is the entry
+    point's (include/frad_hip.h): the terms in ascending source order from 0.0, with a multiply and an add in place of the fma.
+    For a bridge without ``clips_resample``, and the kernel tests' model.  -> (ndarray [rows, C], out_off)"""
+    src = np.asarray(src, np.float64).reshape(-1)
+    h = resample_taps(up, down)
+    half = 10 * max(up, down)
+    terms = 2 * half // up + 1
+    pieces, out_off = [], [0]
+    for j in range(len(src_off)):
+        rows, s0 = int(src_rows[j]), int(src_row0[j])
+        x = src[int(src_off[j]):int(src_off[j]) + rows * C].reshape(rows, C)
+        n = int(out_row0[j]) + np.arange(int(valid[j]), dtype=np.int64)
+        lo = np.maximum(np.maximum(-(-(n * down - half) // up), 0), s0)
+        hi = np.minimum((n * down + half) // up, s0 + rows - 1)
+        acc = np.zeros((len(n), C))
+        for t in range(terms):
+            i = lo + t
+            live = i <= hi
+            if not live.any():
+                break
+            at = np.where(live, i - s0, 0)
+            k = np.where(live, n * down - i * up + half, 0)
+            acc = np.where(live[:, None], acc + x[at] * h[k][:, None], acc) if rows else acc
+        pieces.append(acc)
+        out_off.append(out_off[-1] + len(acc))
+    out = np.concatenate(pieces) if pieces else np.zeros((0, C))
+    if out_format is not None:
+        out = from_f64(out, out_format)
+    return out, np.asarray(out_off, np.int64)
+
+
 class StreamIndex:
     """The frame index of a set of complete streams: one header scan (``frad_asfh_scan`` over all of them, no device work) and the
     per-stream plan of ``decode_batch``, kept for any number of ``decode`` calls.  ``fix_error`` belongs to the index: how a
@@ -117,8 +195,24 @@ class StreamIndex:
         R = p.tail_key[1] if p.tail_key is not None else 0
         return cut, N - cut, m, R, m * cut, R if R else (N - cut if m else 0)
 
+    def samples_at(self, srate: int) -> list:
+        """``samples`` at ``srate``: the rows of every stream resampled to it, ceil(samples * up / down), from the headers alone
+        -- None for a fallback stream"""
+        if srate < 1:
+            raise ValueError(f"a sample rate is at least 1 (got {srate})")
+        out = []
+        for i, p in enumerate(self.plans):
+            if p is None or (self.samples[i] and not p.srate):
+                out.append(None)
+            elif not self.samples[i] or p.srate == srate:
+                out.append(self.samples[i])
+            else:
+                up, down, _ = resample_ratio(srate, p.srate)
+                out.append(resample_rows(self.samples[i], up, down))
+        return out
+
     def decode(self, windows, *, pad_to: int | None = None, out_format: str | None = None, device_inflate: bool = False,
-               as_tensor: bool = False, max_batch_bytes: int = 1 << 30) -> WindowResult:
+               as_tensor: bool = False, max_batch_bytes: int = 1 << 30, srate: int | None = None) -> WindowResult:
         """Decode ``windows``, a sequence of ``(stream, start, length)``: rows ``start : start + length`` of stream ``stream`` of
         the index (``length`` None: to the end; a window is clipped to the stream's end; a stream may be named any number of
         times).  ``out_format``, ``device_inflate``, ``as_tensor`` and ``max_batch_bytes`` mean what they mean for
@@ -126,7 +220,17 @@ class StreamIndex:
         [len(windows), T, C] -- an ndarray of ``out_format``'s dtype (float64 without one), or with ``as_tensor`` a device tensor
         (float64, or the uint8 bytes [B, T, C * itemsize] of ``out_format``) -- rows past ``res.lengths[k]`` hold the format's
         silence, and ``res.pcm[k]`` are views into it; ValueError when the streams used differ in channel count or a window is
-        longer than T."""
+        longer than T.
+
+        ``srate=R``: the windows are taken from every stream resampled to R Hz -- ``start``, ``length`` and ``pad_to`` count
+        rows at R, ``samples_at(R)`` gives the streams' lengths.  The arithmetic is ``scipy.signal.resample_poly``'s (polyphase,
+        zero extension, Kaiser beta = 5; include/frad_hip.h, frad_clips_resample): the source rows a window reads are decoded to
+        float64 by the path above and one ``frad_clips_resample`` per ratio resamples, converts and writes them, so a window is
+        bit for bit the slice of the whole resampled stream.  A stream whose rate is R is not touched: its windows are byte for
+        byte those of the call without ``srate``.  ValueError for R < 1 and for a ratio whose reduced max(up, down) is beyond
+        2048."""
+        if srate is not None:
+            return self._decode_at(srate, windows, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes)
         br = self.bridge
         dt = np.dtype(np.float64) if out_format is None else ff_format_to_numpy_type(out_format)
         if as_tensor and getattr(br, "torch", None) is None:
@@ -212,6 +316,144 @@ class StreamIndex:
             row[b - a:] = silence
             if not host:
                 dense[k] = br.torch.from_numpy(row if out_format is None else row.view(np.uint8)).to(br.device)
+        if dense is not None:
+            if not as_tensor and not isinstance(dense, np.ndarray):
+                dense = dense.cpu().numpy().view(dt)           # one download of the whole batch
+            res.batch = dense
+            for k in range(len(wins)):
+                view = dense[k, :res.lengths[k]]
+                res.pcm[k] = view.reshape(-1) if as_tensor and out_format is not None else view
+        return res
+
+    # -------------------------------------------------------------------------------------------- windows at one sample rate
+    def _decode_at(self, R, windows, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes) -> WindowResult:
+        """``decode`` with ``srate=R``: the windows of streams at R through ``decode`` itself, the others as source windows
+        through ``decode`` (float64, on the device where the bridge keeps tensors) and then one ``clips_resample`` per ratio and
+        channel count."""
+        br = self.bridge
+        if R < 1:
+            raise ValueError(f"a sample rate is at least 1 (got {R})")
+        dt = np.dtype(np.float64) if out_format is None else ff_format_to_numpy_type(out_format)
+        on_dev = getattr(br, "clips_resample", None)
+        if as_tensor and getattr(br, "torch", None) is None:
+            raise ValueError("as_tensor needs a bridge that keeps tensors on the device")
+        wins = []
+        for i, start, length in windows:
+            if not 0 <= i < len(self.streams):
+                raise IndexError(f"stream {i} is not in the index")
+            if start < 0 or (length is not None and length < 0):
+                raise ValueError(f"a window needs start >= 0 and length >= 0 (got {start}, {length})")
+            wins.append((i, start, length))
+        res = WindowResult(len(wins))
+        kw = dict(device_inflate=device_inflate, max_batch_bytes=max_batch_bytes)
+        # ---- a fallback stream is decoded whole, to float64: its rate and length are known only then
+        whole, rate, rows_in, chans = {}, {}, {}, {}
+        for i in sorted({w[0] for w in wins}):
+            p = self.plans[i]
+            if p is None:
+                got = decode_batch([self.streams[i]], fix_error=self.fix_error, device_inflate=device_inflate, bridge=br)
+                whole[i], rate[i] = np.ascontiguousarray(got.pcm[0], np.float64), got.srate[0]
+                rows_in[i], chans[i] = whole[i].shape
+            else:
+                rate[i], rows_in[i], chans[i] = p.srate, self.samples[i], p.channels
+        res.fallback = sorted(whole)
+        ratio = {}
+        for i in rate:
+            if rows_in[i] and rate[i] != R:
+                if not rate[i]:
+                    raise ValueError(f"stream {i} does not say its sample rate")
+                ratio[i] = resample_ratio(R, rate[i])[:2]
+                if max(ratio[i]) > RESAMPLE_MAX:
+                    raise ValueError(f"resampling {rate[i]} Hz to {R} Hz needs {ratio[i][0]}/{ratio[i][1]}: beyond {RESAMPLE_MAX}")
+        # ---- every window as rows [a, b) of its resampled stream, clipped, and the source rows [lo, hi) those read
+        spans, needs = [], []
+        for k, (i, start, length) in enumerate(wins):
+            total = resample_rows(rows_in[i], *ratio[i]) if i in ratio else rows_in[i]
+            a = min(start, total)
+            b = total if length is None else max(a, min(start + length, total))
+            spans.append((a, b))
+            res.lengths[k] = b - a
+            needs.append(resample_needs(a, b, *ratio[i], rows_in[i]) if i in ratio else (a, b))
+        if pad_to is not None:
+            if len({chans[i] for i, _, _ in wins}) > 1:
+                raise ValueError(f"a dense batch needs one channel count (the streams used have {sorted({chans[i] for i, _, _ in wins})})")
+            if any(n > pad_to for n in res.lengths):
+                raise ValueError(f"a window is longer than pad_to = {pad_to}")
+        same = [k for k, w in enumerate(wins) if w[0] not in ratio]
+        other = [k for k, w in enumerate(wins) if w[0] in ratio]
+        dense = None
+        if pad_to is not None:
+            C = chans[wins[0][0]] if wins else 0
+            if on_dev is not None:
+                t = br.torch
+                dense = t.empty((len(wins), pad_to, C), dtype=t.float64, device=br.device) if out_format is None else \
+                    t.empty((len(wins), pad_to, C * dt.itemsize), dtype=t.uint8, device=br.device)
+            else:
+                dense = np.empty((len(wins), pad_to, C), dt)
+        # ---- the streams at R: the path without srate, with the caller's own windows
+        if same:
+            keep = as_tensor if dense is None else not isinstance(dense, np.ndarray)     # (a device batch is filled on the device)
+            got = self.decode([wins[k] for k in same], pad_to=pad_to, out_format=out_format, as_tensor=keep, **kw)
+            if dense is None:
+                for n, k in enumerate(same):
+                    res.pcm[k] = got.pcm[n]
+            elif isinstance(dense, np.ndarray):
+                dense[same] = got.batch
+            else:
+                dense[br.torch.as_tensor(same, device=br.device)] = got.batch
+        # ---- the others: their source rows as float64 (planned streams: one more decode; fallback streams: the whole stream
+        # once, shared by its windows), then one clips_resample per (up, down, channels)
+        planned = [k for k in other if self.plans[wins[k][0]] is not None and needs[k][1] > needs[k][0]]
+        pieces = {}
+        if planned:
+            got = self.decode([(wins[k][0], needs[k][0], needs[k][1] - needs[k][0]) for k in planned], as_tensor=on_dev is not None, **kw)
+            pieces = {k: got.pcm[n] for n, k in enumerate(planned)}
+        groups = {}
+        for k in other:
+            i = wins[k][0]
+            groups.setdefault(ratio[i] + (chans[i],), []).append(k)
+        for (up, down, C), members in groups.items():
+            parts, at, placed = [], 0, {}
+            n = len(members)
+            src_off, src_row0, src_rows = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+            out_row0, valid = np.zeros(n, np.int64), np.zeros(n, np.int32)
+            for j, k in enumerate(members):
+                i, (a, b), (lo, hi) = wins[k][0], spans[k], needs[k]
+                out_row0[j], valid[j] = a, b - a
+                if hi <= lo:
+                    continue
+                if i in whole:                                # the whole stream is one span, placed once
+                    if i not in placed:
+                        placed[i] = at
+                        parts.append(whole[i].reshape(-1))
+                        at += whole[i].size
+                    src_off[j], src_row0[j], src_rows[j] = placed[i], 0, rows_in[i]
+                else:
+                    src_off[j], src_row0[j], src_rows[j] = at, lo, hi - lo
+                    parts.append(pieces[k].reshape(-1))
+                    at += (hi - lo) * C
+            if on_dev is None:
+                src = np.concatenate([np.asarray(x, np.float64) for x in parts]) if parts else np.zeros(0)
+                out, out_off = clips_resample_host(src, src_off, src_row0, src_rows, C, up, down, out_row0, valid, out_format)
+                for j, k in enumerate(members):
+                    piece = out[int(out_off[j]):int(out_off[j + 1])]
+                    if dense is None:
+                        res.pcm[k] = piece
+                    else:
+                        dense[k, :len(piece)] = piece
+                        dense[k, len(piece):] = from_f64(np.zeros(1), dense.dtype)
+                continue
+            t = br.torch
+            parts = [x if isinstance(x, t.Tensor) else t.from_numpy(np.ascontiguousarray(x, np.float64)).to(br.device) for x in parts]
+            src = None if not parts else parts[0] if len(parts) == 1 else t.cat(parts)
+            if dense is not None:
+                on_dev(src, src_off, src_row0, src_rows, C, up, down, out_row0, valid, out_format, span=np.full(n, pad_to, np.int64),
+                       dst_row=np.asarray(members, np.int64) * pad_to, out=dense)
+                continue
+            out, out_off = on_dev(src, src_off, src_row0, src_rows, C, up, down, out_row0, valid, out_format, as_tensor=as_tensor)
+            step = C * dt.itemsize if as_tensor and out_format is not None else 1
+            for j, k in enumerate(members):
+                res.pcm[k] = out[int(out_off[j]) * step:int(out_off[j + 1]) * step]
         if dense is not None:
             if not as_tensor and not isinstance(dense, np.ndarray):
                 dense = dense.cpu().numpy().view(dt)           # one download of the whole batch

@@ -402,6 +402,33 @@ int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const in
                           const int64_t* skip, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
                           const int64_t* out_off, int64_t out_rows, void* stream);
 
+/* frad_clips_resample: polyphase sample-rate conversion of many ragged float64 spans in one pass, with frad_clips_window_add's
+ * output side (all arrays in device memory).  The arithmetic is scipy.signal.resample_poly's with default arguments (zero
+ * extension, Kaiser beta = 5): with M = max(up, down) and half_len = 10 * M the caller computes, in float64,
+ *   taps[k] = sinc((k - half_len) / M) / M * kaiser(2 * half_len + 1, 5.0)[k], normalised to sum 1, times up,   k = 0 .. 2 * half_len
+ * and output row n of a stream is
+ *   y[n][c] = sum over i ascending of x[i][c] * taps[n * down - i * up + half_len],
+ *             max(0, ceil((n * down - half_len) / up)) <= i <= floor((n * down + half_len) / up), i inside the clip's span,
+ * evaluated as acc = fma(x, tap, acc) from acc = 0.0 in that order on every path, so a row's bits do not depend on the window
+ * that asked for it.  n * down and i * up are 64-bit.
+ *   src         float64: clip j's source rows are src_rows[j] rows of C doubles at element offset src_off[j]; they are rows
+ *               src_row0[j] .. of the stream's own timeline (src_row0[j] >= 0).  Rows outside the span count as zero: the
+ *               stream's ends, or rows the caller knows no output row of the clip reads.  Spans of different clips may overlap
+ *               or coincide.  src may be NULL when every src_rows[j] is 0.
+ *   out_row0    int64 [n_clips] >= 0: row r < valid[j] of clip j's span is y[out_row0[j] + r].
+ *   valid, dst_row, out_off, out_rows, out_dtype, flags, out, stream: frad_clips_window_add's -- rows from valid[j] to the end
+ *               of the span are the conversion of 0.0, spans are disjoint, nothing outside them is written, a span leaves in
+ *               16-byte stores where its address allows it and element by element elsewhere.
+ * A block stages the source rows its run of output rows reads in LDS when the run lies inside one clip and they fit, and reads
+ * them from global memory otherwise; the taps are read through L2.  No scratch memory.
+ * The tables are the caller's to check (core.clips_resample does).  FRAD_E_INVALID for C < 1, up < 1, down < 1, half_len != 10 *
+ * max(up, down), the dtype, negative counts and, with rows to write, a null table (dst_row and src may be NULL); FRAD_OK
+ * without a launch for n_clips == 0 or out_rows == 0.                                                                       */
+int frad_clips_resample(const double* src, const int64_t* src_off, const int64_t* src_row0, const int32_t* src_rows, int64_t n_clips,
+                        int32_t C, int32_t up, int32_t down, const double* taps, int32_t half_len, const int64_t* out_row0,
+                        const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off,
+                        int64_t out_rows, void* stream);
+
 /* frad_clips_frame_cut == the Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one pass: fixed-length
  * rows gathered from arbitrary sample-frame offsets of ONE buffer that holds all clips back to back (all arrays in device
  * memory).  With rb = row_len * step bytes per row,
