@@ -51,6 +51,8 @@ SYMBOLS = {
                                       c_void_p, c_void_p, c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
     "frad_clips_resample": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "frad_clips_remix": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_uint32, c_void_p,
+                                 c_void_p, c_int64, c_void_p]),
     "frad_clips_frame_cut": (STATUS, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "frad_p1_golomb_bound": (c_size_t, [c_int32, c_int32]),
     "frad_p1_golomb_encode": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),

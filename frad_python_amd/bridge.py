@@ -13,7 +13,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
     ``p1_decode_run`` / ``p2_decode_run`` (the fused run), ``compact_decode`` (HipBridge only: device inflate, and frames
     that stay on the device for decode_batch), ``clips_overlap_add``, ``clips_window_add`` (StreamIndex.decode; without it the
     windows are assembled in numpy), ``clips_resample`` (StreamIndex.decode(srate=); without it ``window.clips_resample_host``
-    resamples in numpy), ``torch`` + ``device`` (as_tensor).
+    resamples in numpy), ``clips_remix`` (StreamIndex.decode(channels=); without it ``window.clips_remix_host`` mixes in
+    numpy), ``torch`` + ``device`` (as_tensor).
   * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
     ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
@@ -348,6 +349,20 @@ class HipBridge:
         if not out.numel():
             return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
         return self._down_pcm(out, out_format, (-1, C)), out_off
+
+    def clips_remix(self, srcs: list, mats, C_out, valid=None, out_format=None, span=None, dst_row=None, out=None, as_tensor=False):
+        """The clips' channel mix in one launch (core.clips_remix).  ``srcs``: float64 device tensors or ndarrays [rows, C_in],
+        None for a clip without rows; ``mats``: a matrix per clip, or a dict with one per ``C_in``.  Results as
+        ``clips_window_add`` returns them."""
+        t = self.torch
+        srcs = [x if x is None or isinstance(x, t.Tensor) else t.from_numpy(np.ascontiguousarray(x, np.float64)).to(self.device)
+                for x in srcs]
+        out, out_off = self.core.clips_remix(srcs, mats, C_out, valid, out_format, span, dst_row, out)
+        if as_tensor or dst_row is not None:
+            return out, out_off
+        if not out.numel():
+            return np.zeros((0, C_out), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
+        return self._down_pcm(out, out_format, (-1, C_out)), out_off
 
     # ------------------------------------------------------------------ encode_batch: the clips' PCM, and their frames cut out
     def clips_join(self, clips: list, nbytes: list):

@@ -872,6 +872,114 @@ def clips_resample(src: torch.Tensor | None, src_off, src_row0, src_rows, C: int
     return out, out_off
 
 
+def clips_remix(srcs, mats, C_out: int, valid=None, out_format: str | None = None, span=None, dst_row=None,
+                out: torch.Tensor | None = None):
+    """A channel mix of many ragged float64 spans in one launch (frad_clips_remix), converted and written as ``clips_window_add``
+    writes its windows.
+
+    ``srcs``: a list of float64 device tensors ``[rows_j, C_in_j]``, one per clip -- the channel counts may differ; an entry may
+    be None where ``valid[j]`` is 0.  ``mats``: the clips' matrices ``[C_out, C_in_j]`` (host, float64, finite), as a list with one
+    per clip or a dict with one per distinct ``C_in``.  Output row r < ``valid[j]`` (default ``rows_j``) of clip j is ``mats[j] @
+    srcs[j][r]`` in the entry point's arithmetic (include/frad_hip.h: zero weights are skipped, a multiply and an add per term);
+    the rest of the span of ``span[j]`` sample-frames (default ``valid[j]``) is ``out_format``'s silence; ``dst_row`` and ``out`` as
+    for ``clips_window_add``.  Returns ``(out, out_off)``.  Everything is checked here, on the host, before anything is launched,
+    and the tensors' addresses are taken only here."""
+    srcs = list(srcs)
+    n_clips = len(srcs)
+    if C_out < 1:
+        raise ValueError(f"bad geometry: C_out={C_out}")
+    per_cin = isinstance(mats, dict)
+    if not per_cin:
+        mats = list(mats)
+        if len(mats) != n_clips:
+            raise ValueError("mats needs one matrix per clip (or a dict with one per channel count)")
+    device = next((s.device for s in srcs if s is not None), None)
+    rows, ch, addr = np.zeros(n_clips, np.int64), np.ones(n_clips, np.int32), np.zeros(n_clips, np.int64)
+    for j, s in enumerate(srcs):
+        if s is None:
+            continue
+        _require_cuda(s, f"srcs[{j}]")
+        if s.dtype != torch.float64 or s.dim() != 2 or s.shape[1] < 1:
+            raise ValueError(f"srcs[{j}] must be float64 [rows, channels]")
+        if s.device != device:
+            raise ValueError("the clips must live on one device")
+        rows[j], ch[j] = s.shape
+        addr[j] = s.data_ptr() if s.shape[0] else 0
+        if addr[j] % 8:
+            raise ValueError(f"srcs[{j}] is not 8-byte aligned")
+    va = rows.astype(np.int32) if valid is None else np.ascontiguousarray(valid, np.int32).reshape(-1)
+    if va.size != n_clips or (va < 0).any() or (va > rows).any():
+        raise ValueError("valid needs one entry per clip, 0 <= valid[j] <= the clip's rows")
+    # ---- the matrices: each distinct one placed once
+    placed, flat, at = {}, [], 0
+    mat_off = np.zeros(n_clips, np.int64)
+    for j, s in enumerate(srcs):
+        if s is None:
+            continue                                           # (no row of this clip is read: neither is its matrix)
+        key = int(ch[j]) if per_cin else id(mats[j])
+        if key not in placed:
+            if per_cin and key not in mats:
+                raise ValueError(f"no matrix for the clips of {key} channels")
+            m = np.asarray(mats[key] if per_cin else mats[j], np.float64)
+            if m.ndim != 2 or m.shape != (C_out, int(ch[j])):
+                raise ValueError(f"clip {j} needs a matrix [{C_out}, {int(ch[j])}] (got {list(m.shape)})")
+            if not np.isfinite(m).all():
+                raise ValueError(f"the matrix of clip {j} is not finite")
+            placed[key] = (at, m.shape)
+            flat.append(np.ascontiguousarray(m).reshape(-1))
+            at += m.size
+        elif placed[key][1] != (C_out, int(ch[j])):
+            raise ValueError(f"clip {j} needs a matrix [{C_out}, {int(ch[j])}] (got {list(placed[key][1])})")
+        mat_off[j] = placed[key][0]
+    sp = va.astype(np.int64) if span is None else np.ascontiguousarray(span, np.int64).reshape(-1)
+    if sp.size != n_clips or (sp < va).any():
+        raise ValueError("a span must hold its clip's valid rows")
+    out_off = np.zeros(n_clips + 1, np.int64)
+    np.cumsum(sp, out=out_off[1:])
+    total = int(out_off[-1])
+    code = pcm_dtype_code(out_format) if out_format is not None else pcm_dtype_code("f64le")
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    dst = None
+    if dst_row is None:
+        if out is not None:
+            raise ValueError("out goes with dst_row")
+        out = torch.empty((total, C_out), dtype=torch.float64, device=device) if out_format is None else \
+            _pcm_out_tensor(out_format, (total, C_out), device, slack=16)
+    else:
+        dst = np.ascontiguousarray(dst_row, np.int64).reshape(-1)
+        if out is None or dst.size != n_clips:
+            raise ValueError("dst_row needs out and one entry per clip")
+        _require_cuda(out, "out")
+        if out.dtype != (torch.float64 if out_format is None else torch.uint8):
+            raise TypeError("out must be float64, or with out_format the uint8 bytes of that format")
+        if out.device != device:
+            raise ValueError("out must live on the clips' device")
+        have = out.numel() * out.element_size() // (C_out * itemsize_of(code))
+        if (dst < 0).any() or (dst > have - sp).any():
+            raise ValueError(f"a span lies outside out ({have} sample-frames)")
+        order = np.argsort(dst, kind="stable")
+        order = order[sp[order] > 0]
+        if (dst[order][:-1] + sp[order][:-1] > dst[order][1:]).any():
+            raise ValueError("the spans overlap")
+    if total == 0 or n_clips == 0:
+        return out, out_off
+    _require_frame_count(n_clips, "clips")
+    # every table in one upload: int64 src_ptr | mat_off | out_off | dst_row, float64 matrices, int32 src_ch | valid
+    weights = np.concatenate(flat) if flat else np.zeros(1)
+    parts = [addr, mat_off, out_off] + ([dst] if dst is not None else []) + [weights, ch, va]
+    table = np.concatenate([a.view(np.uint8) for a in parts])
+    dev = torch.from_numpy(table).to(device)
+    p, at, ptr = dev.data_ptr(), 0, []
+    for a in parts:
+        ptr.append(p + at)
+        at += a.nbytes
+    with torch.cuda.device(device):
+        _lib.load().clips_remix(ptr[0], ptr[-2], ptr[-3], ptr[1], n_clips, C_out, ptr[-1], ptr[3] if dst is not None else 0, code,
+                                _lib.FRAD_RAW_BE_INTS, out.data_ptr(), ptr[2], total, _stream_ptr())
+    return out, out_off
+
+
 def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: int) -> torch.Tensor:
     """The Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one launch (frad_clips_frame_cut).
 

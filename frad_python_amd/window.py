@@ -15,7 +15,11 @@ per-stream ``Decoder``, as ``decode_batch`` does, sliced on the host and listed 
 
 ``index.decode(..., srate=R)`` takes the windows from every stream resampled to R Hz: the source rows a window
 reads are decoded as above, to float64 on the device, and one launch of ``frad_clips_resample`` per ratio -- ``scipy.signal.
-resample_poly``'s arithmetic -- resamples, converts and writes them, so that streams of mixed rates give one dense batch."""
+resample_poly``'s arithmetic -- resamples, converts and writes them, so that streams of mixed rates give one dense batch.
+
+``index.decode(..., channels=K)`` gives every window with K channels: the windows are decoded (and resampled) as
+above, to float64 on the device, and one launch of ``frad_clips_remix`` per call applies each stream's matrix [K, C_in], converts
+and writes them, so that mono and stereo streams give one dense [B, T, K] batch."""
 from __future__ import annotations
 
 import functools
@@ -157,6 +161,40 @@ def clips_resample_host(src, src_off, src_row0, src_rows, C, up, down, out_row0,
     return out, np.asarray(out_off, np.int64)
 
 
+def remix_matrix(c_in: int, channels: int):
+    """The float64 matrix [channels, c_in] of ``StreamIndex.decode(channels=)`` for a stream of ``c_in`` channels: the identity
+    for ``c_in == channels``, the mean (every weight ``1.0 / c_in``) for one output channel, the mono channel copied to every
+    output channel for ``c_in == 1`` -- and None for anything else: the project does not invent down-mix coefficients."""
+    if c_in == channels:
+        return np.eye(channels)
+    if channels == 1:
+        return np.full((1, c_in), 1.0 / c_in)
+    if c_in == 1:
+        return np.ones((channels, 1))
+    return None
+
+
+def clips_remix_host(x, matrix, out_format=None):
+    """What ``frad_clips_remix`` computes for one clip, in numpy: rows ``x`` [rows, C_in] mixed by ``matrix`` [K, C_in] -> [rows, K].
+    The definition is the entry point's (include/frad_hip.h): for output channel k the terms are the c, ascending, with
+    ``matrix[k][c] != 0.0``; the first sets the sum, every later one is a rounded multiply and a rounded add; a row of the matrix
+    without a non-zero entry gives +0.0.  For a bridge without ``clips_remix``, and the kernel tests' model."""
+    x = np.asarray(x, np.float64)
+    m = np.asarray(matrix, np.float64)
+    x = x.reshape(-1, m.shape[1])
+    out = np.zeros((len(x), m.shape[0]))
+    with np.errstate(all="ignore"):
+        for k in range(m.shape[0]):
+            first = True
+            for c in range(m.shape[1]):
+                if m[k, c] == 0.0:
+                    continue
+                p = x[:, c] * m[k, c]
+                out[:, k] = p if first else out[:, k] + p
+                first = False
+    return out if out_format is None else from_f64(out, out_format)
+
+
 class StreamIndex:
     """The frame index of a set of complete streams: one header scan (``frad_asfh_scan`` over all of them, no device work) and the
     per-stream plan of ``decode_batch``, kept for any number of ``decode`` calls.  ``fix_error`` belongs to the index: how a
@@ -212,7 +250,8 @@ class StreamIndex:
         return out
 
     def decode(self, windows, *, pad_to: int | None = None, out_format: str | None = None, device_inflate: bool = False,
-               as_tensor: bool = False, max_batch_bytes: int = 1 << 30, srate: int | None = None) -> WindowResult:
+               as_tensor: bool = False, max_batch_bytes: int = 1 << 30, srate: int | None = None, channels: int | None = None,
+               mix: dict | None = None) -> WindowResult:
         """Decode ``windows``, a sequence of ``(stream, start, length)``: rows ``start : start + length`` of stream ``stream`` of
         the index (``length`` None: to the end; a window is clipped to the stream's end; a stream may be named any number of
         times).  ``out_format``, ``device_inflate``, ``as_tensor`` and ``max_batch_bytes`` mean what they mean for
@@ -228,7 +267,20 @@ class StreamIndex:
         float64 by the path above and one ``frad_clips_resample`` per ratio resamples, converts and writes them, so a window is
         bit for bit the slice of the whole resampled stream.  A stream whose rate is R is not touched: its windows are byte for
         byte those of the call without ``srate``.  ValueError for R < 1 and for a ratio whose reduced max(up, down) is beyond
-        2048."""
+        2048.
+
+        ``channels=K``: every window has K channels, whatever its stream has.  A stream of ``C_in`` channels is
+        mixed by a float64 matrix [K, C_in]: the identity for ``C_in == K``, the mean for K = 1, the mono channel copied K times
+        for ``C_in == 1``; anything else needs ``mix={C_in: matrix}``, which also overrides the rule for that ``C_in``
+        (``mix`` alone: K is the matrices' own, and every stream used needs an entry).  The order is decode, resample, mix,
+        ``out_format``: the windows are decoded (and resampled) to float64 as above, and one ``frad_clips_remix`` mixes,
+        converts, pads and writes all of them -- ``res.pcm[k]`` is bit for bit ``from_f64(clips_remix_host(X_k, M), out_format)``
+        of the float64 window ``X_k`` the call without ``channels`` and ``out_format`` gives -- so ``pad_to`` takes streams of
+        mixed channel counts: ``res.batch`` is [B, T, K].  ValueError, before anything is decoded, for K < 1, a matrix that is not
+        finite, not [K, C_in] or of another K, and a stream without a matrix (a fallback stream's channel count is known only
+        once it is decoded: for it the last is raised then, before anything is mixed)."""
+        if channels is not None or mix is not None:
+            return self._decode_mixed(windows, channels, mix, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes, srate)
         if srate is not None:
             return self._decode_at(srate, windows, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes)
         br = self.bridge
@@ -461,6 +513,113 @@ class StreamIndex:
             for k in range(len(wins)):
                 view = dense[k, :res.lengths[k]]
                 res.pcm[k] = view.reshape(-1) if as_tensor and out_format is not None else view
+        return res
+
+    # ------------------------------------------------------------------------------------------- windows of K channels each
+    def _decode_mixed(self, windows, channels, mix, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes, srate) -> WindowResult:
+        """``decode`` with ``channels`` or ``mix``: the windows as float64 through ``decode`` itself (on the device where the
+        bridge keeps tensors), then one ``clips_remix`` that mixes, converts, pads and writes all of them."""
+        br = self.bridge
+        # ---- the arguments, before anything is decoded
+        if channels is not None and (isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or channels < 1):
+            raise ValueError(f"channels is a count of at least 1 (got {channels!r})")
+        given = {}
+        for c_in, m in (mix or {}).items():
+            if isinstance(c_in, bool) or not isinstance(c_in, (int, np.integer)) or c_in < 1:
+                raise ValueError(f"mix is keyed by channel counts (got {c_in!r})")
+            try:
+                m = np.array(m, np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"mix[{c_in}] is not a float64 matrix: {e}") from None
+            if m.ndim != 2 or m.shape[1] != c_in or m.shape[0] < 1:
+                raise ValueError(f"mix[{c_in}] must be a matrix [channels, {c_in}] (got {list(m.shape)})")
+            if not np.isfinite(m).all():
+                raise ValueError(f"mix[{c_in}] is not finite")
+            given[int(c_in)] = m
+        K = int(channels) if channels is not None else None
+        for c_in, m in given.items():
+            if K is None:
+                K = m.shape[0]
+            if m.shape[0] != K:
+                raise ValueError(f"mix[{c_in}] gives {m.shape[0]} channels, not {K}")
+        if K is None:
+            raise ValueError("mix is empty and channels is not given")
+        if as_tensor and getattr(br, "torch", None) is None:
+            raise ValueError("as_tensor needs a bridge that keeps tensors on the device")
+        if srate is not None and srate < 1:
+            raise ValueError(f"a sample rate is at least 1 (got {srate})")
+        wins = []
+        for i, start, length in windows:
+            if not 0 <= i < len(self.streams):
+                raise IndexError(f"stream {i} is not in the index")
+            if start < 0 or (length is not None and length < 0):
+                raise ValueError(f"a window needs start >= 0 and length >= 0 (got {start}, {length})")
+            wins.append((i, start, length))
+        mats = {}
+
+        def matrix(i, c_in):
+            if c_in not in mats:
+                m = given.get(c_in)
+                if m is None and channels is not None:
+                    m = remix_matrix(c_in, K)
+                if m is None:
+                    raise ValueError(f"stream {i} has {c_in} channels: mix has no matrix [{K}, {c_in}] for it")
+                mats[c_in] = m
+            return mats[c_in]
+
+        for i in sorted({w[0] for w in wins}):
+            if self.plans[i] is not None:
+                matrix(i, self.plans[i].channels)
+        if pad_to is not None:                                 # (a fallback stream's length is known once it is decoded: below)
+            totals = self.samples if srate is None else self.samples_at(srate)
+            if any(totals[i] is not None and min(totals[i] - min(start, totals[i]), totals[i] if length is None else length) > pad_to
+                   for i, start, length in wins):
+                raise ValueError(f"a window is longer than pad_to = {pad_to}")
+        # ---- the windows as float64, ragged
+        dt = np.dtype(np.float64) if out_format is None else ff_format_to_numpy_type(out_format)
+        on_dev = getattr(br, "clips_remix", None)
+        got = self.decode(wins, device_inflate=device_inflate, max_batch_bytes=max_batch_bytes, srate=srate,
+                          as_tensor=getattr(br, "torch", None) is not None)
+        n = len(wins)
+        res = WindowResult(n)
+        res.lengths, res.fallback = got.lengths, got.fallback
+        for k in range(n):
+            matrix(wins[k][0], int(got.pcm[k].shape[1]))
+        if pad_to is not None and any(rows > pad_to for rows in res.lengths):
+            raise ValueError(f"a window is longer than pad_to = {pad_to}")
+        # ---- the mix: the only conversion to out_format, and the only stage that writes the result
+        if on_dev is None:
+            pieces = [clips_remix_host(np.asarray(x), mats[int(x.shape[1])], out_format) for x in got.pcm]
+            if pad_to is None:
+                res.pcm = pieces
+                return res
+            res.batch = np.empty((n, pad_to, K), dt)
+            silence = from_f64(np.zeros(1), dt)
+            for k, piece in enumerate(pieces):
+                res.batch[k, :len(piece)] = piece
+                res.batch[k, len(piece):] = silence
+                res.pcm[k] = res.batch[k, :len(piece)]
+            return res
+        t = br.torch
+        valid = np.asarray(res.lengths, np.int32)
+        if pad_to is None:
+            if n:
+                out, out_off = on_dev(got.pcm, mats, K, valid, out_format, as_tensor=as_tensor)
+                step = K * dt.itemsize if as_tensor and out_format is not None else 1
+                for k in range(n):
+                    res.pcm[k] = out[int(out_off[k]) * step:int(out_off[k + 1]) * step]
+            return res
+        dense = t.empty((n, pad_to, K), dtype=t.float64, device=br.device) if out_format is None else \
+            t.empty((n, pad_to, K * dt.itemsize), dtype=t.uint8, device=br.device)
+        if n and pad_to:
+            on_dev(got.pcm, mats, K, valid, out_format, span=np.full(n, pad_to, np.int64), dst_row=np.arange(n, dtype=np.int64) * pad_to,
+                   out=dense)
+        if not as_tensor:
+            dense = dense.cpu().numpy().view(dt)               # one download of the whole batch
+        res.batch = dense
+        for k in range(n):
+            view = dense[k, :res.lengths[k]]
+            res.pcm[k] = view.reshape(-1) if as_tensor and out_format is not None else view
         return res
 
     # ------------------------------------------------------------------------------------------------ what a window needs

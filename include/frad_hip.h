@@ -429,6 +429,33 @@ int frad_clips_resample(const double* src, const int64_t* src_off, const int64_t
                         const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out, const int64_t* out_off,
                         int64_t out_rows, void* stream);
 
+/* frad_clips_remix: a channel mix of many ragged float64 spans whose channel count differs per clip, in one pass, with
+ * frad_clips_window_add's output side (all arrays in device memory).  Clip j has src_ch[j] = C_in channels and a float64 matrix
+ * M[C_out][C_in]; for one source row x[0 .. C_in) and output channel k
+ *   the terms are the c, ascending, with M[k][c] != 0.0; the first sets acc = x[c] * M[k][c], every later one does
+ *   acc = acc + x[c] * M[k][c] -- a rounded multiply, then a rounded add, never an fma; a row of M without a non-zero entry
+ *   gives +0.0.
+ * Skipping the zero weights is part of the definition: an identity or permutation row copies the source's bits (-0.0,
+ * denormals, +-Inf; x * 1.0 is exact), no Inf * 0 is ever formed, and the result equals the elementwise numpy model
+ * (window.clips_remix_host) bit for bit for every matrix.
+ *   src_ptr     [n_clips] device addresses: clip j's valid[j] rows of src_ch[j] doubles, 8-byte aligned.  A table of pointers,
+ *               not a base and offsets: the windows of one call come out of several launches' allocations.  src_ptr[j] may be
+ *               NULL where valid[j] == 0.
+ *   src_ch      int32 [n_clips] >= 1.
+ *   mats        float64; clip j's matrix is the C_out * src_ch[j] doubles at element mat_off[j] (int64 [n_clips]), row-major
+ *               [C_out][C_in].  Clips may share one.
+ *   valid, dst_row, out_off, out_rows, out_dtype, flags, out, stream: frad_clips_window_add's -- rows from valid[j] to the end
+ *               of the span are the conversion of 0.0, spans are disjoint, nothing outside them is written, a span leaves in
+ *               16-byte stores where its address allows it and element by element elsewhere.  The launch is partitioned by
+ *               out_off in units of C_out elements.
+ * A source row's values are read once per row and store, two at a time where the address is 16-byte aligned; the matrices are
+ * read through the caches.  No LDS, no scratch memory.
+ * The tables are the caller's to check (core.clips_remix does).  FRAD_E_INVALID for C_out < 1, the dtype, negative counts and,
+ * with rows to write, a null table (dst_row may be NULL); FRAD_OK without a launch for n_clips == 0 or out_rows == 0.       */
+int frad_clips_remix(const double* const* src_ptr, const int32_t* src_ch, const double* mats, const int64_t* mat_off, int64_t n_clips,
+                     int32_t C_out, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
+                     const int64_t* out_off, int64_t out_rows, void* stream);
+
 /* frad_clips_frame_cut == the Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one pass: fixed-length
  * rows gathered from arbitrary sample-frame offsets of ONE buffer that holds all clips back to back (all arrays in device
  * memory).  With rb = row_len * step bytes per row,
