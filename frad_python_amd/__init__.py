@@ -14,6 +14,7 @@ from .decoder import Decoder, DecodeResult  # noqa: F401
 from .repairer import Repairer  # noqa: F401
 from .batch import decode_batch, BatchResult, encode_batch, EncodeBatchResult  # noqa: F401
 from .window import StreamIndex, WindowResult, decode_windows  # noqa: F401
+from .spectral import Spectral  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "encode_batch", "EncodeBatchResult",
-           "StreamIndex", "WindowResult", "decode_windows", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]
+           "StreamIndex", "WindowResult", "decode_windows", "Spectral", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]

@@ -44,6 +44,7 @@ class HipBridge:
         self.scan_lib = core._lib.load()                      # frad_asfh_scan: the decoder's native header scanner
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._resample_taps = {}                              # (up, down) -> the taps on the device (clips_resample)
+        self._spectrum_tables = {}                            # SpecTables.key -> (the tables, their upload) (clips_spectrum)
 
     def _up(self, data: bytes):
         """host bytes -> device uint8 tensor, straight from the caller's (read-only) buffer; a device tensor (the frame block
@@ -363,6 +364,23 @@ class HipBridge:
         if not out.numel():
             return np.zeros((0, C_out), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
         return self._down_pcm(out, out_format, (-1, C_out)), out_off
+
+    def clips_spectrum(self, srcs: list, valid, tables, K, frame_off, out=None):
+        """The clips' spectrograms in one launch (core.clips_spectrum).  ``srcs``: float64 device tensors or ndarrays [rows, K],
+        None for a clip without rows; ``tables``: a ``spectral.SpecTables``, checked and uploaded once per distinct ``key`` and
+        kept on the device.  -> the device tensor [frame_off[-1], K, n_bins] (``out`` when given)."""
+        t = self.torch
+        srcs = [x if x is None or isinstance(x, t.Tensor) else t.from_numpy(np.ascontiguousarray(x, np.float64)).to(self.device)
+                for x in srcs]
+        cache, dev = self._spectrum_tables, None
+        if tables.key is not None:
+            if tables.key not in cache or cache[tables.key][0] is not tables:
+                self.core.spectrum_tables_check(tables)
+                if len(cache) >= 64:
+                    cache.clear()
+                cache[tables.key] = (tables, self.core.spectrum_tables_upload(tables, self.device))
+            dev = cache[tables.key][1]
+        return self.core.clips_spectrum(srcs, valid, tables, K, frame_off, out, dev)
 
     # ------------------------------------------------------------------ encode_batch: the clips' PCM, and their frames cut out
     def clips_join(self, clips: list, nbytes: list):

@@ -980,6 +980,111 @@ def clips_remix(srcs, mats, C_out: int, valid=None, out_format: str | None = Non
     return out, out_off
 
 
+def spectrum_tables_check(tb) -> None:
+    """The host checks of a ``spectral.SpecTables`` for ``clips_spectrum`` (ValueError): geometry, window, bands, logarithm."""
+    n_fft = tb.n_fft
+    if n_fft not in (128, 256, 512, 1024, 2048, 4096):
+        raise ValueError(f"n_fft is a power of two from 128 to 4096 (got {n_fft})")
+    if tb.hop < 1 or tb.power not in (1, 2):
+        raise ValueError(f"bad geometry: hop={tb.hop}, power={tb.power}")
+    w = np.asarray(tb.window)
+    if w.dtype != np.float64 or w.shape != (n_fft,) or not np.isfinite(w).all():
+        raise ValueError(f"the window must be {n_fft} finite float64 weights (win_length <= n_fft, zero-padded)")
+    if np.dtype(tb.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"the output is float32 or float64 (got {tb.dtype})")
+    if tb.band_lo is not None:
+        lo, ln, off, bw = (np.asarray(a) for a in (tb.band_lo, tb.band_len, tb.band_off, tb.band_w))
+        if lo.dtype != np.int32 or ln.dtype != np.int32 or off.dtype != np.int64 or bw.dtype != np.float64 or bw.ndim != 1:
+            raise ValueError("the bands are int32 band_lo / band_len, int64 band_off and float64 weights")
+        if not (lo.shape == ln.shape == off.shape) or lo.ndim != 1 or lo.size < 1:
+            raise ValueError("band_lo, band_len and band_off need one entry per output bin")
+        if (lo < 0).any() or (ln < 0).any() or (lo.astype(np.int64) + ln > n_fft // 2 + 1).any():
+            raise ValueError(f"a band leaves the bins [0, {n_fft // 2}]")
+        if (off < 0).any() or (off + ln > bw.size).any():
+            raise ValueError("a band leaves the weight array")
+        if not np.isfinite(bw).all():
+            raise ValueError("the filterbank is not finite")
+    if tb.log_scale:
+        if not (np.isfinite(tb.log_scale) and np.isfinite(tb.floor) and tb.floor > 0 and np.isfinite(tb.floor_log)):
+            raise ValueError(f"a logarithm needs a finite floor > 0 (got {tb.floor})")
+
+
+def spectrum_tables_upload(tb, device) -> dict:
+    """the window and the bands of a checked ``SpecTables`` in one upload -> what ``clips_spectrum(dev_tables=)`` takes"""
+    has = tb.band_lo is not None
+    parts = [np.ascontiguousarray(tb.window, np.float64)]
+    if has:
+        parts += [np.ascontiguousarray(tb.band_w, np.float64), np.ascontiguousarray(tb.band_off, np.int64),
+                  np.ascontiguousarray(tb.band_lo, np.int32), np.ascontiguousarray(tb.band_len, np.int32)]
+    dev = torch.from_numpy(np.concatenate([a.view(np.uint8) for a in parts] + [np.zeros(8, np.uint8)])).to(device)
+    ptr, at = [], dev.data_ptr()
+    for a in parts:
+        ptr.append(at)
+        at += a.nbytes
+    return dict(keep=dev, window=ptr[0], band_w=ptr[1] if has else 0, band_off=ptr[2] if has else 0, band_lo=ptr[3] if has else 0,
+                band_len=ptr[4] if has else 0, n_bands=len(tb.band_lo) if has else 0, n_weights=len(tb.band_w) if has else 0)
+
+
+def clips_spectrum(srcs, valid, tb, K: int, frame_off, out: torch.Tensor | None = None, dev_tables: dict | None = None) -> torch.Tensor:
+    """Spectrograms of many ragged float64 windows in one launch (frad_clips_spectrum; include/frad_hip.h).
+
+    ``srcs``: a list of float64 device tensors ``[rows_j, K]``, one per clip (None where ``valid[j]`` is 0); ``valid[j] <=
+    rows_j`` (default ``rows_j``): the rows that count, every other row is zero.  ``tb``: a ``spectral.SpecTables`` (host):
+    geometry, window, bands, logarithm, output type.  ``frame_off`` int64 ``[n_clips + 1]``, ascending: clip j owns the frames
+    ``frame_off[j] : frame_off[j + 1]`` of the output, the first of them its frame 0 -- ``j * F`` for a dense batch.  ``out``:
+    ``[frame_off[-1], K, n_bins]`` of the tables' dtype (allocated when None).  ``dev_tables``: ``spectrum_tables_upload(tb,
+    device)`` kept by the caller, so that a spec's tables are uploaded once.  Everything is checked here, on the host, before
+    anything is launched, and the tensors' addresses are taken only here."""
+    srcs = list(srcs)
+    n_clips = len(srcs)
+    if K < 1:
+        raise ValueError(f"bad geometry: K={K}")
+    spectrum_tables_check(tb)
+    device = next((s.device for s in srcs if s is not None), None)
+    rows, addr = np.zeros(n_clips, np.int64), np.zeros(n_clips, np.int64)
+    for j, s in enumerate(srcs):
+        if s is None:
+            continue
+        _require_cuda(s, f"srcs[{j}]")
+        if s.dtype != torch.float64 or s.dim() != 2 or s.shape[1] != K:
+            raise ValueError(f"srcs[{j}] must be float64 [rows, {K}]")
+        if s.device != device:
+            raise ValueError("the clips must live on one device")
+        rows[j] = s.shape[0]
+        addr[j] = s.data_ptr() if s.shape[0] else 0
+        if addr[j] % 8:
+            raise ValueError(f"srcs[{j}] is not 8-byte aligned")
+    va = rows.astype(np.int32) if valid is None else np.ascontiguousarray(valid, np.int32).reshape(-1)
+    if va.size != n_clips or (va < 0).any() or (va > rows).any():
+        raise ValueError("valid needs one entry per clip, 0 <= valid[j] <= the clip's rows")
+    off = np.ascontiguousarray(frame_off, np.int64).reshape(-1)
+    if off.size != n_clips + 1 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("frame_off needs n_clips + 1 ascending entries from 0")
+    total = int(off[-1])
+    tdt = torch.float32 if np.dtype(tb.dtype) == np.dtype(np.float32) else torch.float64
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = torch.empty((total, K, tb.n_bins), dtype=tdt, device=device)
+    else:
+        _require_cuda(out, "out")
+        if out.dtype != tdt or out.numel() != total * K * tb.n_bins or out.device != device:
+            raise ValueError(f"out must be {total} * {K} * {tb.n_bins} values of {tdt} on the clips' device")
+    if total == 0 or n_clips == 0:
+        return out
+    _require_frame_count(n_clips, "clips")
+    dt = dev_tables if dev_tables is not None else spectrum_tables_upload(tb, device)
+    parts = [addr, off, va]                                    # int64 src_ptr | frame_off, int32 valid: one upload
+    dev = torch.from_numpy(np.concatenate([a.view(np.uint8) for a in parts])).to(device)
+    p = dev.data_ptr()
+    code = pcm_dtype_code("f32le" if tdt == torch.float32 else "f64le")
+    with torch.cuda.device(device):
+        _lib.load().clips_spectrum(p, p + addr.nbytes + off.nbytes, n_clips, K, p + addr.nbytes, total, tb.n_fft, tb.hop, int(tb.center),
+                                   dt["window"], tb.power, dt["n_bands"], dt["band_lo"], dt["band_len"], dt["band_off"], dt["band_w"],
+                                   dt["n_weights"], tb.log_scale, tb.floor, tb.floor_log, code, out.data_ptr(), _stream_ptr())
+    return out
+
+
 def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: int) -> torch.Tensor:
     """The Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one launch (frad_clips_frame_cut).
 

@@ -19,7 +19,12 @@ resample_poly``'s arithmetic -- resamples, converts and writes them, so that str
 
 ``index.decode(..., channels=K)`` gives every window with K channels: the windows are decoded (and resampled) as
 above, to float64 on the device, and one launch of ``frad_clips_remix`` per call applies each stream's matrix [K, C_in], converts
-and writes them, so that mono and stereo streams give one dense [B, T, K] batch."""
+and writes them, so that mono and stereo streams give one dense [B, T, K] batch.
+
+``index.decode(..., features=spec)`` returns spectrograms instead of samples (``spectral.Spectral``): the windows
+are decoded, resampled and mixed as above, to float64 on the device, and one launch of ``frad_clips_spectrum`` per call frames,
+windows and transforms them, applies the filterbank and the logarithm and writes ``[F, K, n_bins]`` per window or one dense
+``[B, F, K, n_bins]`` batch."""
 from __future__ import annotations
 
 import functools
@@ -30,18 +35,21 @@ import numpy as np
 from .backend.pcmformat import ff_format_to_numpy_type, from_f64
 from .batch import _frames, _plan, _scan_together, clips_overlap_host, decode_batch
 from .frames import repair
+from .spectral import Spectral, clips_spectrum_host
 
 
 class WindowResult:
     """``pcm[k]`` [rows_k, channels] of window k; ``lengths[k]`` = rows_k; ``batch``: with ``pad_to=T`` the dense [B, T, C] block
     (``pcm[k]`` are then views into it), else None; ``fallback``: the sorted indices of the streams a per-stream ``Decoder``
-    decoded."""
+    decoded.  With ``features=``: ``features[k]`` [frames_k, K, n_bins], ``frames[k]``, ``feature_batch`` [B, F, K, n_bins] with
+    ``pad_to`` (else None), and ``pcm`` / ``batch`` are None unless ``keep_pcm``; without it the three are None."""
 
     def __init__(self, n: int):
         self.pcm = [None] * n
         self.lengths = [0] * n
         self.batch = None
         self.fallback = []
+        self.features = self.frames = self.feature_batch = None
 
 
 def select_frames(a: int, b: int, cut: int, L: int, m: int, has_tail: bool):
@@ -251,7 +259,7 @@ class StreamIndex:
 
     def decode(self, windows, *, pad_to: int | None = None, out_format: str | None = None, device_inflate: bool = False,
                as_tensor: bool = False, max_batch_bytes: int = 1 << 30, srate: int | None = None, channels: int | None = None,
-               mix: dict | None = None) -> WindowResult:
+               mix: dict | None = None, features: Spectral | None = None, keep_pcm: bool = False) -> WindowResult:
         """Decode ``windows``, a sequence of ``(stream, start, length)``: rows ``start : start + length`` of stream ``stream`` of
         the index (``length`` None: to the end; a window is clipped to the stream's end; a stream may be named any number of
         times).  ``out_format``, ``device_inflate``, ``as_tensor`` and ``max_batch_bytes`` mean what they mean for
@@ -278,7 +286,27 @@ class StreamIndex:
         of the float64 window ``X_k`` the call without ``channels`` and ``out_format`` gives -- so ``pad_to`` takes streams of
         mixed channel counts: ``res.batch`` is [B, T, K].  ValueError, before anything is decoded, for K < 1, a matrix that is not
         finite, not [K, C_in] or of another K, and a stream without a matrix (a fallback stream's channel count is known only
-        once it is decoded: for it the last is raised then, before anything is mixed)."""
+        once it is decoded: for it the last is raised then, before anything is mixed).
+
+        ``features=spec`` (a ``spectral.Spectral``): the result is the spectrogram of every window.  The order is
+        decode, resample, mix, features: the spectral stage reads the float64 windows ``X_k`` [rows_k, K] that the same call
+        without ``features`` gives, rows outside a window counting as zero, and one ``frad_clips_spectrum`` writes all of them:
+        ``res.features[k]`` is ``[frames_k, K, n_bins]`` of the spec's dtype -- ``spectral.clips_spectrum_host(X_k, spec)`` within
+        the transform's float64 rounding -- and ``res.frames[k]`` the frame count of the window's own length
+        (``spec.frames(rows_k)``).  With ``pad_to=T`` every window has ``F = spec.frames(T)`` frames, ``res.feature_batch`` is the
+        dense ``[B, F, K, n_bins]`` block (``.permute(0, 2, 3, 1)`` is torch's ``[B, K, n_bins, F]``, a view) and
+        ``res.features[k]`` its first ``frames_k`` frames, bit for bit those of the ragged call.  The streams used need one
+        channel count (``channels=`` gives it).  A mel bank is built for ``srate``, else for the one rate of the streams used.
+        ``res.pcm`` and ``res.batch`` are None unless ``keep_pcm``: then they are those of the call without ``features``.
+        ValueError, before anything is decoded, for ``out_format`` together with ``features``, ``pad_to < n_fft`` without
+        ``center``, streams of several rates under a mel bank without ``srate``, a mel bank whose ``fmax`` is beyond half the
+        rate, and streams of several channel counts (for a fallback stream what depends on the stream is raised once it is
+        decoded).  ``keep_pcm`` without ``features`` is a ValueError too."""
+        if features is not None:
+            return self._decode_features(features, keep_pcm, windows, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes, srate,
+                                         channels, mix)
+        if keep_pcm:
+            raise ValueError("keep_pcm goes with features")
         if channels is not None or mix is not None:
             return self._decode_mixed(windows, channels, mix, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes, srate)
         if srate is not None:
@@ -620,6 +648,82 @@ class StreamIndex:
         for k in range(n):
             view = dense[k, :res.lengths[k]]
             res.pcm[k] = view.reshape(-1) if as_tensor and out_format is not None else view
+        return res
+
+    # ---------------------------------------------------------------------------------------------- spectrograms of the windows
+    def _decode_features(self, spec, keep_pcm, windows, pad_to, out_format, device_inflate, as_tensor, max_batch_bytes, srate, channels,
+                         mix) -> WindowResult:
+        """``decode`` with ``features``: the windows as float64 through ``decode`` itself (on the device where the bridge keeps
+        tensors), then one ``clips_spectrum`` over all of them."""
+        br = self.bridge
+        # ---- the arguments, before anything is decoded
+        if not isinstance(spec, Spectral):
+            raise ValueError(f"features is a spectral.Spectral (got {type(spec).__name__})")
+        if out_format is not None:
+            raise ValueError("features reads the float64 windows: out_format does not go with it")
+        if pad_to is not None and not spec.center and pad_to < spec.n_fft:
+            raise ValueError(f"pad_to = {pad_to} is shorter than one frame of n_fft = {spec.n_fft}")
+        on_torch = getattr(br, "torch", None) is not None
+        if as_tensor and not on_torch:
+            raise ValueError("as_tensor needs a bridge that keeps tensors on the device")
+        if srate is not None and srate < 1:
+            raise ValueError(f"a sample rate is at least 1 (got {srate})")
+        wins = [tuple(w) for w in windows]
+        used = sorted({w[0] for w in wins if isinstance(w[0], (int, np.integer)) and 0 <= w[0] < len(self.streams)})
+        planned = [i for i in used if self.plans[i] is not None]
+        rate = srate
+        if spec.needs_rate and srate is None:
+            rates = {self.plans[i].srate or None for i in planned} | ({None} if len(planned) < len(used) else set())
+            if len(rates) > 1 or None in rates:                # (a fallback stream's rate is not known from its headers)
+                raise ValueError(f"a mel filterbank needs one known sample rate (the streams used have {sorted(rates, key=str)}): give srate=")
+            rate = rates.pop() if rates else None
+        tb = spec.tables(rate) if not spec.needs_rate or rate else None          # (None: a mel bank and no stream, nothing to compute)
+        n_bins = tb.n_bins if tb is not None else spec.n_mels
+        if channels is None and mix is None and len({self.plans[i].channels for i in planned}) > 1:
+            raise ValueError(f"features need one channel count (the streams used have {sorted({self.plans[i].channels for i in planned})}): "
+                             "give channels=")
+        # ---- the windows as float64: ragged, or the dense batch whose rows past a window's length are zero
+        got = self.decode(wins, pad_to=pad_to, device_inflate=device_inflate, max_batch_bytes=max_batch_bytes, srate=srate,
+                          channels=channels, mix=mix, as_tensor=on_torch)
+        n = len(wins)
+        res = WindowResult(n)
+        res.lengths, res.fallback = got.lengths, got.fallback
+        chans = {int(x.shape[1]) for x in got.pcm}
+        if len(chans) > 1:
+            raise ValueError(f"features need one channel count (the streams used have {sorted(chans)}): give channels=")
+        K = chans.pop() if chans else (int(got.batch.shape[2]) if got.batch is not None else 0)
+        res.frames = [spec.frames(rows) for rows in res.lengths]
+        F = spec.frames(pad_to) if pad_to is not None else None
+        counts = res.frames if F is None else [F] * n
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(counts, out=off[1:])
+        if keep_pcm:
+            down = (lambda x: x) if as_tensor or not on_torch else (lambda x: x.cpu().numpy())
+            if got.batch is not None:
+                res.batch = down(got.batch)
+                res.pcm = [res.batch[k, :res.lengths[k]] for k in range(n)]
+            else:
+                res.pcm = [down(x) for x in got.pcm]
+        else:
+            res.pcm = None
+        # ---- the spectral stage: the only one that writes the result
+        on_dev = getattr(br, "clips_spectrum", None)
+        if on_dev is None:
+            pieces = [clips_spectrum_host(np.asarray(x), tb, rows=pad_to) for x in got.pcm]
+            flat = np.concatenate(pieces) if pieces else np.zeros((0, K, n_bins), spec.dtype)
+        elif n and off[-1] and K:
+            flat = on_dev(got.pcm, np.asarray(res.lengths, np.int32), tb, K, off)
+            if not as_tensor:
+                flat = flat.cpu().numpy()                      # one download of the whole result
+        elif as_tensor:
+            flat = br.torch.empty((0, K, n_bins), dtype=br.torch.float32 if spec.dtype == np.float32 else br.torch.float64, device=br.device)
+        else:
+            flat = np.zeros((0, K, n_bins), spec.dtype)
+        if F is None:
+            res.features = [flat[int(off[k]):int(off[k + 1])] for k in range(n)]
+        else:
+            res.feature_batch = flat.reshape(n, F, K, n_bins)
+            res.features = [res.feature_batch[k, :min(res.frames[k], F)] for k in range(n)]
         return res
 
     # ------------------------------------------------------------------------------------------------ what a window needs

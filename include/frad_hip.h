@@ -456,6 +456,35 @@ int frad_clips_remix(const double* const* src_ptr, const int32_t* src_ch, const 
                      int32_t C_out, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
                      const int64_t* out_off, int64_t out_rows, void* stream);
 
+/* frad_clips_spectrum: power / magnitude / (log-)filterbank spectrogram of many ragged float64 windows in one pass (all arrays
+ * in device memory).  Clip j is valid[j] rows of K doubles at src_ptr[j]; every row outside [0, valid[j])
+ * counts as +0.0.  With N = n_fft, frame f of a clip and channel c:
+ *   x[n]  = row f * hop + n - (center ? N/2 : 0), channel c, times window[n]          n = 0 .. N-1 (a rounded product)
+ *   X[k]  = sum_n x[n] exp(-2 pi i k n / N)                                            k = 0 .. N/2, unnormalised, float64
+ *   P[k]  = Re^2 + Im^2 (power = 2), or its square root (power = 1)
+ *   v[m]  = P[m] (n_bands = 0: N/2 + 1 values), or acc from +0.0 of acc = acc + band_w[band_off[m] + i] * P[band_lo[m] + i],
+ *           i = 0 .. band_len[m] - 1 ascending (a rounded multiply, a rounded add; a band of length 0 gives +0.0)
+ *   y[m]  = v[m] (log_scale = 0), or v[m] <= floor ? floor_log : log_scale * log(v[m]); floor_log is the caller's
+ *           log_scale * log(floor), stored as given, so that every clamped value is one constant whatever the device's log
+ *   out   = y rounded to nearest: float32 (out_dtype FRAD_PCM_F32LE) or float64 (FRAD_PCM_F64LE)
+ * X is computed as an N/2-point complex FFT of the packed sequence (fft_team, twiddles from the plan tables) and one split
+ * pass: the error against the exact sum is that of a radix FFT in float64.  An all-zero frame gives P = +0.0 exactly.  A
+ * frame's values depend only on its N inputs and the tables, not on the launch around it.
+ *   frame_off   int64 [n_clips + 1], ascending: clip j owns the frames frame_off[j] .. frame_off[j+1] - 1 of the launch, the
+ *               first of them its frame 0.  Frames at or beyond out_frames are not computed.
+ *   out         [out_frames, K, n_out] values, n_out = n_bands or N/2 + 1: one frame-channel's values are contiguous.  A dense
+ *               batch [B, F, K, n_out] is frame_off[j] = j * F.  Nothing else is written.
+ *   window      float64 [N]; band_lo, band_len int32 [n_bands]; band_off int64 [n_bands]; band_w float64 [n_weights].
+ * N is a power of two from 128 to 4096.  One LDS-resident transform per frame-channel, no scratch memory.
+ * The tables are the caller's to check (core.clips_spectrum does); a band that leaves [0, N/2] or band_w is cut short, never
+ * read.  FRAD_E_INVALID for N, hop < 1, K < 1, center not 0/1, power not 1/2, the dtype, negative counts, a logarithm without
+ * finite floor > 0 and floor_log, and, with frames to write, a null table; FRAD_OK without a launch for n_clips == 0 or
+ * out_frames == 0.                                                                                                          */
+int frad_clips_spectrum(const double* const* src_ptr, const int32_t* valid, int64_t n_clips, int32_t K, const int64_t* frame_off,
+                        int64_t out_frames, int32_t n_fft, int32_t hop, int32_t center, const double* window, int32_t power,
+                        int32_t n_bands, const int32_t* band_lo, const int32_t* band_len, const int64_t* band_off, const double* band_w,
+                        int64_t n_weights, double log_scale, double floor, double floor_log, int32_t out_dtype, void* out, void* stream);
+
 /* frad_clips_frame_cut == the Encoder's frame cut (encoder.py:72-93) for the frames of many clips in one pass: fixed-length
  * rows gathered from arbitrary sample-frame offsets of ONE buffer that holds all clips back to back (all arrays in device
  * memory).  With rb = row_len * step bytes per row,
