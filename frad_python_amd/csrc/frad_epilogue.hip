@@ -80,8 +80,8 @@ __global__ void __launch_bounds__(256) k_from_f64(const unsigned char* __restric
 // instead of two (decoder.py:28-46, then src/decoder.py:23 from_f64(...).astype(fmt))
 template <int KIND, int LGS>
 __global__ void __launch_bounds__(256) k_p1_ola_pcm(const double* __restrict__ frames, long long n_frames, int N, int C, int cut,
-                                                    const double* __restrict__ prev_tail, unsigned char* __restrict__ out,
-                                                    double* __restrict__ next_tail, int be, int raw_be) {
+                                                    const double* __restrict__ prev_tail, const double* __restrict__ win,
+                                                    unsigned char* __restrict__ out, double* __restrict__ next_tail, int be, int raw_be) {
     constexpr int EPT = 16 >> LGS;
     const long long n = n_frames * (long long)cut * C;
     const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(256) k_p1_ola_pcm(const double* __restrict__ f
         u64 b[EPT];
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const double x = i0 + e < n ? p1_ola_value(frames, prev_tail, N, C, cut, i0 + e) : 0.0;
+            const double x = i0 + e < n ? p1_ola_value(frames, prev_tail, win, N, C, cut, i0 + e) : 0.0;
             b[e] = from_f64_bits<KIND, LGS>(x, raw_be != 0 && be);
             if (be) b[e] = swap_elem<LGS>(b[e]);
         }
@@ -116,10 +116,11 @@ __global__ void __launch_bounds__(256) k_p1_ola_pcm(const double* __restrict__ f
 
 // One output row of the clip-aware overlap-add: where row r of a clip (of m * cut + tail rows, or + L flush rows) comes from.
 // Decoder.overlap + flush() (decoder.py:28-46, 110-114) per clip: the equal-length frames cross-fade as p1_ola_value does (same
-// operation order, same cos arguments), the clip's first frame is not faded, a last frame of another length is faded over its
-// first L rows and written whole, and without one the last frame's rows [cut, N) follow unfaded.  `tail_win` (optional,
-// hanning_in_overlap(L) as the host computes it): the weights of a last frame whose own overlap length differs from L -- the
-// frame the Decoder cross-fades on the host, in numpy, because the carried fragment has another geometry (decoder.py:207-209).
+// operation order, the same weights: `hann` = hann_table(L)), the clip's first frame is not faded, a last frame of another length
+// is faded over its first L rows and written whole, and without one the last frame's rows [cut, N) follow unfaded.  `tail_win`
+// (optional, hanning_in_overlap(L) as the caller computes it): the weights of a last frame whose own overlap length differs from
+// L -- the frame the Decoder cross-fades on the host, in numpy, because the carried fragment has another geometry
+// (decoder.py:207-209).
 struct ClipRow {
     const double* src;                                         // the row's C samples
     const double* prev;                                        // the row it is faded against, or nullptr
@@ -131,10 +132,9 @@ struct ClipCur {                                               // the clip a lan
 };
 
 __device__ __forceinline__ ClipRow clips_ola_row(const double* __restrict__ frames, int N, int C, int cut, int ratio,
-                                                 const double* __restrict__ tails, const double* __restrict__ tail_win, const ClipCur& k,
-                                                 long long r) {
+                                                 const double* __restrict__ tails, const double* __restrict__ tail_win,
+                                                 const double* __restrict__ hann, const ClipCur& k, long long r) {
     const int L = N - cut;
-    const double pi = 3.141592653589793;
     const long long body = k.m * cut;
     ClipRow o;
     o.prev = nullptr; o.w_in = 1.0; o.w_out = 0.0;
@@ -160,11 +160,8 @@ __device__ __forceinline__ ClipRow clips_ola_row(const double* __restrict__ fram
         }
     }
     if (o.prev != nullptr) {
-        if (table) { o.w_in = tail_win[n]; o.w_out = tail_win[L - 1 - n]; }
-        else {
-            o.w_in = 0.5 * (1.0 - cos(pi * (double)(n + 1) / (double)(L + 1)));
-            o.w_out = 0.5 * (1.0 - cos(pi * (double)(L - n) / (double)(L + 1)));
-        }
+        const double* w = table ? tail_win : hann;
+        o.w_in = w[n]; o.w_out = w[L - 1 - n];
     }
     return o;
 }
@@ -180,8 +177,9 @@ template <int KIND, int LGS>
 __global__ void __launch_bounds__(256) k_clips_ola(const double* __restrict__ frames, const int64_t* __restrict__ clip_frame0, long long n_clips,
                                                    int N, int C, int cut, int ratio, const double* __restrict__ tails,
                                                    const int64_t* __restrict__ tail_off, const int32_t* __restrict__ tail_rows,
-                                                   const double* __restrict__ tail_win, unsigned char* __restrict__ out,
-                                                   const int64_t* __restrict__ out_off, long long out_rows, int be, int raw_be) {
+                                                   const double* __restrict__ tail_win, const double* __restrict__ hann,
+                                                   unsigned char* __restrict__ out, const int64_t* __restrict__ out_off, long long out_rows,
+                                                   int be, int raw_be) {
     constexpr int EPT = 16 >> LGS;
     long long last = out_off[n_clips];
     if (last > out_rows) last = out_rows;                      // never beyond what the caller sized
@@ -218,7 +216,7 @@ __global__ void __launch_bounds__(256) k_clips_ola(const double* __restrict__ fr
                 if (i0 + e < n && i0 + e >= n0) {
                     if (row.src == nullptr || c == 0) {
                         while (s >= k.end && k.j + 1 < n_clips) enter(k, k.j + 1);
-                        row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, k, s - k.base);
+                        row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, hann, k, s - k.base);
                     }
                     x = row.src[c];
                     if (row.prev != nullptr) {
@@ -278,7 +276,8 @@ struct WinTables {                                             // the per-clip t
 template <int KIND, int LGS>
 __global__ void __launch_bounds__(256) k_clips_win(const double* __restrict__ frames, WinTables t, long long n_clips, int N, int C, int cut,
                                                    int ratio, const double* __restrict__ tails, const double* __restrict__ tail_win,
-                                                   unsigned char* __restrict__ out, long long out_rows, int be, int raw_be) {
+                                                   const double* __restrict__ hann, unsigned char* __restrict__ out, long long out_rows,
+                                                   int be, int raw_be) {
     constexpr int EPT = 16 >> LGS;
     long long last = t.out_off[n_clips];
     if (last > out_rows) last = out_rows;                      // never beyond what the caller sized
@@ -326,7 +325,7 @@ __global__ void __launch_bounds__(256) k_clips_win(const double* __restrict__ fr
                         while (s >= k.end && k.j + 1 < n_clips) enter(k, k.j + 1);
                         const long long r = s - k.base;
                         pad = r >= k.valid;
-                        if (!pad) row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, k, k.skip + r);
+                        if (!pad) row = clips_ola_row(frames, N, C, cut, ratio, tails, tail_win, hann, k, k.skip + r);
                         have = true;
                     }
                     if (!pad) {
@@ -539,7 +538,9 @@ int frad_p1_overlap_add_pcm(const double* frames, int64_t n_frames, int32_t N, i
     const dim3 grid((unsigned)blocks), blk(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned char* o = static_cast<unsigned char*>(ola_out);
-#define GO(K, L) hipLaunchKernelGGL((k_p1_ola_pcm<K, L>), grid, blk, 0, s, frames, (long long)n_frames, N, C, cut, prev_tail, o, next_tail, be, raw)
+    const double* win = nullptr;
+    if (const int rc = hann_table(N - cut, &win)) return rc;
+#define GO(K, L) hipLaunchKernelGGL((k_p1_ola_pcm<K, L>), grid, blk, 0, s, frames, (long long)n_frames, N, C, cut, prev_tail, win, o, next_tail, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
         case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;
@@ -568,8 +569,10 @@ int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int
     const dim3 grid((unsigned)blocks), blk(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned char* o = static_cast<unsigned char*>(out);
+    const double* hann = nullptr;                              // (no overlap: cut = N and nothing is faded)
+    if (N > cut) if (const int rc = hann_table(N - cut, &hann)) return rc;
 #define GO(K, L) hipLaunchKernelGGL((k_clips_ola<K, L>), grid, blk, 0, s, frames, clip_frame0, (long long)n_clips, N, C, cut, ratio, tails, \
-                                    tail_off, tail_rows, tail_win, o, out_off, (long long)out_rows, be, raw)
+                                    tail_off, tail_rows, tail_win, hann, o, out_off, (long long)out_rows, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
         case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;
@@ -600,7 +603,9 @@ int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const in
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned char* o = static_cast<unsigned char*>(out);
     const WinTables t{clip_f0, clip_m, tail_off, tail_rows, skip, valid, dst_row, out_off};
-#define GO(K, L) hipLaunchKernelGGL((k_clips_win<K, L>), grid, blk, 0, s, frames, t, (long long)n_clips, N, C, cut, ratio, tails, tail_win, o, \
+    const double* hann = nullptr;                              // (no overlap: cut = N and nothing is faded)
+    if (N > cut) if (const int rc = hann_table(N - cut, &hann)) return rc;
+#define GO(K, L) hipLaunchKernelGGL((k_clips_win<K, L>), grid, blk, 0, s, frames, t, (long long)n_clips, N, C, cut, ratio, tails, tail_win, hann, o, \
                                     (long long)out_rows, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;

@@ -165,6 +165,10 @@ const double* deq_table() {
     return d;
 }
 
+// hanning_in_overlap(L) (backend/__init__.py:3): w[i] = 0.5 (1 - cos(pi (i + 1) / (L + 1))), i < L, in float64 with the host's cos
+// as numpy evaluates it for the reference
+std::map<std::pair<int, int>, double*> g_hann;
+
 P1Wave wave_tables(const P1Tables& tb, int N) {
     P1Wave pw{};
     pw.deq = nullptr;
@@ -190,6 +194,26 @@ void p1_clear() {                                            // frad_plan_clear:
     g_band.clear();
     for (auto& kv : g_deq) (void)hipFree(kv.second);
     g_deq.clear();
+    for (auto& kv : g_hann) (void)hipFree(kv.second);
+    g_hann.clear();
+}
+int hann_table(int L, const double** out) {
+    if (L < 1) return FRAD_E_INVALID;
+    int dev = 0; FRAD_HIPCHK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_band_mu);
+    const auto key = std::make_pair(dev, L);
+    auto it = g_hann.find(key);
+    if (it != g_hann.end()) { *out = it->second; return FRAD_OK; }
+    // kept until frad_plan_clear like the band maps, so that no launch in flight loses its table: L = ceil(N / ratio), and all
+    // 255 ratios of one frame size together come to about 44 N bytes
+    const double pi = 3.141592653589793;
+    std::vector<double> host((size_t)L);
+    for (int i = 0; i < L; ++i) host[i] = 0.5 * (1.0 - cos(pi * (double)(i + 1) / (double)(L + 1)));
+    double* d = nullptr;
+    if (hipMalloc(&d, sizeof(double) * (size_t)L) != hipSuccess) return FRAD_E_NOMEM;
+    if (const hipError_t e = hipMemcpy(d, host.data(), sizeof(double) * (size_t)L, hipMemcpyHostToDevice)) { (void)hipFree(d); FRAD_HIPCHK(e); }
+    g_hann[key] = d; *out = d;
+    return FRAD_OK;
 }
 }  // namespace frad
 
@@ -443,8 +467,10 @@ int frad_p1_overlap_add(const double* frames, int64_t n_frames, int32_t N, int32
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
+    const double* win = nullptr;
+    if (const int rc = hann_table(N - cut, &win)) return rc;
     hipLaunchKernelGGL(k_p1_ola<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), frames, (long long)n_frames, N, C,
-                       cut, prev_tail, ola_out, next_tail);
+                       cut, prev_tail, win, ola_out, next_tail);
     FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

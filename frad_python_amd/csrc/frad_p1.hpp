@@ -34,6 +34,9 @@ struct P1Edges { int edge[P1_BANDS + 1]; };
 // frad_global.hip: profile 1 through HBM workspaces (frames wider than a CU's LDS at a non-power-of-two size)
 int global_p1_analogue(const unsigned char* pcm, int32_t* q, int32_t* tq, const Geom& g, const P1Tables& tb, hipStream_t s);
 int global_p1_digital(const int32_t* q, const int32_t* tq, double* out, const Geom& g, const P1Tables& tb, hipStream_t s);
+// frad_p1.hip: the overlap-add's Hann ramp hanning_in_overlap(L) (backend/__init__.py:3) as the reference's host computes it,
+// a device table of L float64 per (device, L).  FRAD_OK or a status
+int hann_table(int L, const double** out);
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
     return u2d(wave_allreduce_u64(d2u(v), [](u64 a, u64 b) { return d2u(u2d(a) + u2d(b)); }));
@@ -626,19 +629,19 @@ __host__ __device__ constexpr int p2_analysis_lds(int N) { return (P2_RED + 16) 
 // R8: decoder overlap-add over a batch of consecutive frames (decoder.py:28-46).  Frame i keeps
 // rows [0, cut) -- its first L = N - cut rows cross-faded with frame i-1's tail -- and hands its
 // own tail [cut, N) to frame i+1.  out: [n_frames, cut, C]; next_tail: [L, C].
-// element i of the overlap-added output [n_frames, cut, C] (decoder.py:31-38, backend/__init__.py:3)
-__device__ __forceinline__ double p1_ola_value(const double* __restrict__ frames, const double* __restrict__ prev_tail, int N, int C, int cut, long long i) {
+// element i of the overlap-added output [n_frames, cut, C] (decoder.py:31-38); win = hann_table(L): the weights are the
+// host's, so that the cross-faded samples are the reference's bit for bit (the device's cos differs from the host's in the last
+// bit for about one argument in 500)
+__device__ __forceinline__ double p1_ola_value(const double* __restrict__ frames, const double* __restrict__ prev_tail,
+                                               const double* __restrict__ win, int N, int C, int cut, long long i) {
     const int L = N - cut;
-    const double pi = 3.141592653589793;
     const long long f = i / ((long long)cut * C);
     const int r = (int)(i - f * (long long)cut * C), n = r / C, c = r - n * C;
     double v = frames[(f * N + n) * C + c];
     if (n < L) {
         const double* tail = f > 0 ? frames + ((f - 1) * N + cut) * C : prev_tail;
         if (tail != nullptr) {
-            // hanning_in_overlap (backend/__init__.py:3): w[i] = 0.5 (1 - cos(pi (i+1) / (L+1)))
-            const double w_in = 0.5 * (1.0 - cos(pi * (double)(n + 1) / (double)(L + 1)));
-            const double w_out = 0.5 * (1.0 - cos(pi * (double)(L - n) / (double)(L + 1)));
+            const double w_in = win[n], w_out = win[L - 1 - n];       // fade_in[i], fade_in[olap_len - i - 1] (decoder.py:36-37)
             v = v * w_in;
             v = v + tail[(long long)n * C + c] * w_out;
         }
@@ -648,12 +651,12 @@ __device__ __forceinline__ double p1_ola_value(const double* __restrict__ frames
 
 template <int UNUSED>
 __global__ void __launch_bounds__(256) k_p1_ola(const double* __restrict__ frames, long long n_frames, int N, int C, int cut,
-                                                const double* __restrict__ prev_tail, double* __restrict__ out,
-                                                double* __restrict__ next_tail) {
+                                                const double* __restrict__ prev_tail, const double* __restrict__ win,
+                                                double* __restrict__ out, double* __restrict__ next_tail) {
     const int L = N - cut;
     const long long total = n_frames * (long long)cut * C;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-        out[i] = p1_ola_value(frames, prev_tail, N, C, cut, i);
+        out[i] = p1_ola_value(frames, prev_tail, win, N, C, cut, i);
     if (next_tail != nullptr && n_frames > 0)
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)L * C; i += (long long)gridDim.x * blockDim.x)
             next_tail[i] = frames[((n_frames - 1) * N + cut) * C + i];

@@ -156,7 +156,8 @@ int frad_p1_analogue(const void* pcm, int32_t pcm_dtype, int64_t n_frames, int32
  * backend/__init__.py:3), for overlap_ratio > 1: cut = N*(ratio-1)/ratio; frame i contributes rows [0, cut) to
  * ola_out [n_frames, cut, C], its first N - cut rows cross-faded against frame i-1's tail (`prev_tail`
  * [N - cut, C] for i = 0, NULL = no previous frame: no fade); the last frame's tail is returned in `next_tail`
- * [N - cut, C] for the next batch (or the flush).                                                       */
+ * [N - cut, C] for the next batch (or the flush).  The ramp is a table computed on the host, in float64 with
+ * the host's cos, so the cross-faded samples are the reference's bit for bit.                           */
 int frad_p1_digital(const int32_t* q, const int32_t* tq, int64_t n_frames, int32_t N, int32_t C,
                     int32_t bits, int32_t srate, double* pcm_out, void* stream);
 int frad_p1_overlap_add(const double* frames, int64_t n_frames, int32_t N, int32_t C, int32_t overlap_ratio,
@@ -365,7 +366,8 @@ int frad_p1_digital_pcm(const int32_t* q, const int32_t* tq, int64_t n_frames, i
  *   tail_win    optional float64 [L]: hanning_in_overlap(L) as the caller computed it.  When given, it weights the last frames
  *               whose own overlap length tail_rows - tail_rows*(ratio-1)/ratio differs from L: the Decoder cross-fades those
  *               on the host, because the carried fragment has another geometry (decoder.py:207-209), and this keeps the result
- *               bit-identical to it.  NULL: every weight is computed on the device.
+ *               bit-identical to it.  NULL: every weight is the library's own table of hanning_in_overlap(L), computed on the
+ *               host in float64 as numpy does (the device's cos differs from the host's in the last bit now and then).
  * The offsets are the caller's to check (core.clips_overlap_add does); FRAD_E_INVALID for N, C, the ratio and the dtype.      */
 int frad_clips_overlap_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
                            const double* tails, const int64_t* tail_off, const int32_t* tail_rows, const double* tail_win,
