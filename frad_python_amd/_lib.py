@@ -49,6 +49,8 @@ SYMBOLS = {
                                        c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
     "frad_clips_window_add": (STATUS, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "frad_clips_carry_add": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_uint32, c_void_p,
+                                     c_void_p, c_int64, c_void_p]),
     "frad_clips_resample": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
     "frad_clips_remix": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_uint32, c_void_p,

@@ -14,7 +14,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
     that stay on the device for decode_batch), ``clips_overlap_add``, ``clips_window_add`` (StreamIndex.decode; without it the
     windows are assembled in numpy), ``clips_resample`` (StreamIndex.decode(srate=); without it ``window.clips_resample_host``
     resamples in numpy), ``clips_remix`` (StreamIndex.decode(channels=); without it ``window.clips_remix_host`` mixes in
-    numpy), ``torch`` + ``device`` (as_tensor).
+    numpy), ``clips_carry_add`` (DecoderPool; without it ``pool.clips_carry_host`` cross-fades in numpy), ``torch`` + ``device``
+    (as_tensor).
   * Encoder: ``lossless_encode``, ``p1_encode_bodies`` / ``p2_encode_bodies``; ``p1_encode_payloads`` /
     ``p2_encode_payloads`` for device_deflate=True (``deflate_payloads`` and ``last_deflate_host`` behind them), ``rs_encode``
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
@@ -313,6 +314,35 @@ class HipBridge:
         if not out.numel():
             return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off
         return self._down_pcm(out, out_format, (-1, C)), out_off
+
+    def clips_carry_add(self, frames, clip_frame0, N, C, ratio, prev, out_format=None, as_tensor=False):
+        """The next run of whole frames of many live streams in one launch (core.clips_carry_add: DecoderPool).  ``frames`` as
+        ``clips_overlap_add`` takes them; ``prev``: None, or per clip None or the fragment the stream carried in, a float64
+        device tensor [L, C].  -> (out, out_off, next): ``out`` as ``clips_overlap_add`` returns it; ``next[j]`` is the
+        fragment clip j carries out, on the device -- a view of one block that this call allocates, so it never is a buffer
+        that ``prev`` names -- or ``prev[j]`` itself for a clip without a frame, and None where nothing is carried."""
+        t = self.torch
+        if frames is not None and not isinstance(frames, t.Tensor):
+            frames = t.from_numpy(np.ascontiguousarray(frames, np.float64)).to(self.device)
+        cf = np.asarray(clip_frame0, np.int64).reshape(-1)
+        n = cf.size - 1
+        cut = N * (ratio - 1) // ratio if ratio else N
+        L = N - cut
+        prev = list(prev) if prev is not None else [None] * n
+        nxt = list(prev)
+        if L and n > 0:
+            block = t.empty((n, L, C), dtype=t.float64, device=self.device)
+            for j in np.flatnonzero(np.diff(cf) > 0).tolist():
+                nxt[j] = block[j]
+        out, out_off = self.core.clips_carry_add(frames, cf, N, C, ratio, prev if L else None,
+                                                 [x if x is not p else None for x, p in zip(nxt, prev)] if L else None, out_format)
+        if not L:
+            nxt = [None] * n
+        if as_tensor:
+            return out, out_off, nxt
+        if not out.numel():
+            return np.zeros((0, C), np.float64 if out_format is None else ff_format_to_numpy_type(out_format)), out_off, nxt
+        return self._down_pcm(out, out_format, (-1, C)), out_off, nxt
 
     def clips_window_add(self, frames, clip_f0, clip_m, N, C, ratio, tails: list, tail_off, tail_rows, skip, valid, out_format=None,
                          tail_win=None, span=None, dst_row=None, out=None, as_tensor=False):

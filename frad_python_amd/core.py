@@ -681,6 +681,99 @@ def clips_overlap_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, 
     return out, out_off
 
 
+def _require_device_tensor(t, what: str):
+    """``_require_cuda`` for an operator whose every failed host check is a ValueError"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous tensor in MI355X device memory")
+
+
+def clips_carry_add(frames: torch.Tensor | None, clip_frame0, N: int, C: int, overlap_ratio: int, prev=None, nxt=None,
+                    out_format: str | None = None, out: torch.Tensor | None = None):
+    """``p1_overlap_add`` for many live streams in one launch (frad_clips_carry_add): clip j is the next ``m_j`` whole frames of a
+    stream that is still arriving, cross-faded from the fragment it carried in to the fragment it carries out.
+
+    ``frames`` float64 [n, N, C]; ``clip_frame0`` (host integers, n_clips + 1, non-decreasing, inside ``frames``) says which
+    belong to clip j.  ``prev`` / ``nxt``: None, or per clip None or a float64 device tensor of ``L * C`` elements -- the
+    fragment read, and the buffer that takes rows ``[cut, N)`` of the clip's last frame (left alone when ``m_j == 0``); a clip's
+    two must differ.  With ``overlap_ratio`` 0 nothing is faded or carried.  Returns ``(out, out_off)``: clip j is rows
+    ``out_off[j]:out_off[j+1]`` (``m_j * cut`` of them) of ``out``, float64 [rows, C] or with ``out_format`` that format's
+    bytes as ``p1_overlap_add`` returns them; ``out``, when given, is written from its start and must hold them.  Every table
+    is checked here, on the host, before anything is launched."""
+    cf = np.ascontiguousarray(clip_frame0, np.int64).reshape(-1)
+    n_clips = cf.size - 1
+    if n_clips < 0:
+        raise ValueError("clip_frame0 needs n_clips + 1 entries")
+    if N < 1 or C < 1 or not (overlap_ratio == 0 or 2 <= overlap_ratio <= 256):
+        raise ValueError(f"bad geometry: N={N} C={C} overlap_ratio={overlap_ratio}")
+    cut = N * (overlap_ratio - 1) // overlap_ratio if overlap_ratio else N
+    L = N - cut
+    if cut < 1:
+        raise ValueError(f"bad geometry: N={N} keeps no row at overlap_ratio={overlap_ratio}")
+    if cf[0] < 0 or (np.diff(cf) < 0).any():
+        raise ValueError("clip_frame0 must not be negative and must not decrease")
+    m = np.diff(cf)
+    if cf[-1] > cf[0]:
+        if frames is None:
+            raise ValueError("frames is missing")
+        _require_device_tensor(frames, "frames")
+        if frames.dtype != torch.float64 or frames.numel() % (N * C):
+            raise ValueError(f"frames must be float64 [n, {N}, {C}]")
+        if cf[-1] > frames.numel() // (N * C):
+            raise ValueError("a clip's frames lie outside frames")
+    device = frames.device if frames is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    ptrs = np.zeros((2, max(n_clips, 1)), np.uint64)
+    for row, (name, table) in enumerate((("prev", prev), ("nxt", nxt))):
+        if table is None or not L:
+            continue
+        if len(table) != n_clips:
+            raise ValueError(f"{name} needs one entry per clip")
+        for j, t in enumerate(table):
+            if t is None:
+                continue
+            _require_device_tensor(t, f"{name}[{j}]")
+            if t.dtype != torch.float64 or t.numel() != L * C or t.device != device:
+                raise ValueError(f"{name}[{j}] must be float64 [{L}, {C}] on {device}")
+            if t.data_ptr() % 8:
+                raise ValueError(f"{name}[{j}] must be 8-byte aligned")
+            ptrs[row, j] = t.data_ptr()
+    pp, nn = ptrs[0, :n_clips], ptrs[1, :n_clips]
+    if ((pp != 0) & (pp == nn)).any():
+        raise ValueError("a clip's prev and nxt must be different buffers")
+    rd, wr = np.sort(pp[pp != 0]), nn[(nn != 0) & (m > 0)]
+    if rd.size and wr.size:
+        # no fragment written may be one that is read: the launch reads and writes them in no order
+        span = np.uint64(L * C * 8)
+        at = np.searchsorted(rd, wr + span, side="left")       # the last read that starts below the end of the write ...
+        if ((at > 0) & (rd[np.maximum(at, 1) - 1] + span > wr)).any():             # ... ends above its start
+            raise ValueError("a nxt buffer overlaps a prev buffer")
+    out_off = np.zeros(n_clips + 1, np.int64)
+    np.cumsum(m * cut, out=out_off[1:])
+    total = int(out_off[-1])
+    code = pcm_dtype_code(out_format) if out_format is not None else pcm_dtype_code("f64le")
+    if out is None:
+        out = torch.empty((total, C), dtype=torch.float64, device=device) if out_format is None else \
+            _pcm_out_tensor(out_format, (total, C), device, slack=16)
+    else:
+        _require_device_tensor(out, "out")
+        if out.dtype != (torch.float64 if out_format is None else torch.uint8):
+            raise ValueError("out must be float64, or with out_format the uint8 bytes of that format")
+        if out.numel() * out.element_size() < total * C * itemsize_of(code):
+            raise ValueError(f"out is too small for {total} sample-frames")
+    if total == 0 or n_clips == 0:
+        return out, out_off
+    _require_frame_count(n_clips, "clips")
+    # the four tables in one upload: int64 clip_frame0 | out_off, then the prev and the nxt pointers
+    n1 = n_clips + 1
+    table = np.concatenate([cf.view(np.uint8), out_off.view(np.uint8), ptrs[0, :n_clips].view(np.uint8), ptrs[1, :n_clips].view(np.uint8)])
+    dev = torch.from_numpy(table).to(device)
+    p = dev.data_ptr()
+    with torch.cuda.device(device):
+        _lib.load().clips_carry_add(frames.data_ptr(), p, n_clips, N, C, overlap_ratio, p + 16 * n1 if L else 0,
+                                    p + 16 * n1 + 8 * n_clips if L else 0, code, _lib.FRAD_RAW_BE_INTS, out.data_ptr(), p + 8 * n1, total,
+                                    _stream_ptr())
+    return out, out_off
+
+
 def clips_window_add(frames: torch.Tensor | None, clip_f0, clip_m, N: int, C: int, overlap_ratio: int, tails: torch.Tensor | None = None,
                      tail_off=None, tail_rows=None, skip=None, valid=None, out_format: str | None = None, tail_win=None, span=None,
                      dst_row=None, out: torch.Tensor | None = None):

@@ -11,6 +11,8 @@
 //   k_clips_ola       Decoder.overlap + flush() for many clips in one launch, ragged output (frad_clips_overlap_add).
 //   k_clips_win       k_clips_ola on a row range of every clip, zero-padded and scattered into a dense batch
 //                     (frad_clips_window_add: sample windows, window.py).
+//   k_clips_carry     k_clips_ola for clips that are pieces of live streams: each starts from a carried fragment and ends in
+//                     one (frad_clips_carry_add: DecoderPool, pool.py).
 //   k_clips_cut       the Encoder's frame cut for many clips in one launch: fixed-length rows gathered from one buffer
 //                     (frad_clips_frame_cut).
 //   frad_asfh_scan    host code: walks a FrAD byte stream once and fills a table of frames (tools/asfh.py:98-134,
@@ -346,6 +348,104 @@ __global__ void __launch_bounds__(256) k_clips_win(const double* __restrict__ fr
     }
 }
 
+// frad_clips_carry_add: k_clips_ola's pass for clips that are the next piece of a live stream.  A clip is m whole frames and
+// nothing else (no last frame of another length, no flush fragment): its first frame is faded against the fragment the stream
+// carried in (prev_ptr[j], when there is one), and rows [cut, N) of its last frame leave as the fragment it carries out
+// (next_ptr[j], float64 whatever the output format).  The launch is partitioned by out_off as above (a lane owns 16-byte
+// stores, searches out_off only when a store has left the clip, one row lookup per row); the weights and the operation order
+// are p1_ola_value's, so a clip's rows are frad_p1_overlap_add_pcm's bits.  The fragments are copied by a second grid-stride
+// loop over n_clips * L * C elements; a clip without frames is skipped by both loops, so its pending fragment stays pending.
+struct CarryCur {                                              // the clip a lane is in
+    long long j, base, end, f0;
+    const double* prev;
+};
+template <int KIND, int LGS>
+__global__ void __launch_bounds__(256) k_clips_carry(const double* __restrict__ frames, const int64_t* __restrict__ clip_frame0, long long n_clips,
+                                                     int N, int C, int cut, const double* const* __restrict__ prev_ptr,
+                                                     double* const* __restrict__ next_ptr, const double* __restrict__ hann,
+                                                     unsigned char* __restrict__ out, const int64_t* __restrict__ out_off, long long out_rows,
+                                                     int be, int raw_be) {
+    constexpr int EPT = 16 >> LGS;
+    const int L = N - cut;
+    long long last = out_off[n_clips];
+    if (last > out_rows) last = out_rows;                      // never beyond what the caller sized
+    const long long n = last * C, n0 = (long long)out_off[0] * C;
+    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long tile = 256LL * EPT * CLIPS_K;
+    auto enter = [&](CarryCur& k, long long j) {
+        k.j = j; k.base = out_off[j]; k.end = out_off[j + 1];
+        k.f0 = clip_frame0[j]; k.prev = (L > 0 && prev_ptr != nullptr) ? prev_ptr[j] : nullptr;
+    };
+    for (long long t0 = (long long)blockIdx.x * tile; t0 < n; t0 += (long long)gridDim.x * tile) {
+        CarryCur k;
+        k.j = -1; k.end = 0;
+        for (int it = 0; it < CLIPS_K; ++it) {
+            const long long i0 = t0 + ((long long)it * 256 + threadIdx.x) * EPT;
+            if (i0 >= n) break;
+            long long s;
+            if (n <= 0x7fffffffLL) s = (uint32_t)i0 / (uint32_t)C; else s = i0 / C;
+            int c = (int)(i0 - s * C);
+            if (k.j < 0 || s >= k.end) {                       // the last clip that starts at or before sample-frame s
+                long long lo = k.j < 0 ? 0 : k.j, hi = n_clips;
+                while (hi - lo > 1) {
+                    const long long mid = (lo + hi) >> 1;
+                    if ((long long)out_off[mid] <= s) lo = mid; else hi = mid;
+                }
+                enter(k, lo);
+            }
+            ClipRow row;
+            row.src = nullptr; row.prev = nullptr; row.w_in = 1.0; row.w_out = 0.0;
+            u64 b[EPT];
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) {
+                double x = 0.0;
+                if (i0 + e < n && i0 + e >= n0) {
+                    if (row.src == nullptr || c == 0) {
+                        while (s >= k.end && k.j + 1 < n_clips) enter(k, k.j + 1);
+                        const long long r = s - k.base;
+                        long long f;
+                        int nn;
+                        if (r <= 0x7fffffffLL) { f = (uint32_t)r / (uint32_t)cut; nn = (int)((uint32_t)r - (uint32_t)f * (uint32_t)cut); }
+                        else { f = r / cut; nn = (int)(r - f * cut); }
+                        row.src = frames + ((k.f0 + f) * N + nn) * C;
+                        row.prev = nullptr;
+                        if (nn < L) {
+                            if (f > 0) row.prev = frames + ((k.f0 + f - 1) * N + cut + nn) * C;
+                            else if (k.prev != nullptr) row.prev = k.prev + (long long)nn * C;
+                            if (row.prev != nullptr) { row.w_in = hann[nn]; row.w_out = hann[L - 1 - nn]; }
+                        }
+                    }
+                    x = row.src[c];
+                    if (row.prev != nullptr) {
+                        x = x * row.w_in;
+                        x = x + row.prev[c] * row.w_out;
+                    }
+                }
+                b[e] = from_f64_bits<KIND, LGS>(x, raw_be != 0 && be);
+                if (be) b[e] = swap_elem<LGS>(b[e]);
+                if (++c == C) { c = 0; ++s; }
+            }
+            if (vec && i0 + EPT <= n && i0 >= n0) {
+                FRAD_NT_STORE(pack16<LGS>(b), FRAD_GPTR(v4u, out + (i0 << LGS)));
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPT; ++e) if (i0 + e < n && i0 + e >= n0) store_elem<LGS>(out + ((i0 + e) << LGS), b[e]);
+            }
+        }
+    }
+    if (L > 0 && next_ptr != nullptr) {                        // the fragments carried out: plain copies, bits unchanged
+        const long long per = (long long)L * C, total = n_clips * per;
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+            long long j;
+            if (total <= 0x7fffffffLL) j = (uint32_t)i / (uint32_t)per; else j = i / per;
+            const long long e = i - j * per;
+            const long long f0 = clip_frame0[j], m = clip_frame0[j + 1] - f0;
+            double* const dst = next_ptr[j];
+            if (m > 0 && dst != nullptr) dst[e] = frames[((f0 + m - 1) * N + cut) * C + e];
+        }
+    }
+}
+
 // frad_clips_frame_cut: frad_clips_overlap_add turned round -- the encoder's frame cut for many clips, a streaming pass over
 // the fixed-length output rows.  A block owns a tile of CUT_K * 256 chunks of 16 output bytes, a lane every 256th of them; the
 // chunks sit at 16-byte aligned ADDRESSES (chunk c covers output bytes [16 c - head, 16 c - head + 16), head = out mod 16), so
@@ -607,6 +707,40 @@ int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const in
     if (N > cut) if (const int rc = hann_table(N - cut, &hann)) return rc;
 #define GO(K, L) hipLaunchKernelGGL((k_clips_win<K, L>), grid, blk, 0, s, frames, t, (long long)n_clips, N, C, cut, ratio, tails, tail_win, hann, o, \
                                     (long long)out_rows, be, raw)
+    switch (kind * 4 + lg) {
+        case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
+        case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;
+        case 9: GO(2, 1); break; case 10: GO(2, 2); break; case 11: GO(2, 3); break;
+        default: return FRAD_E_INVALID;
+    }
+#undef GO
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+int frad_clips_carry_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
+                         const double* const* prev_ptr, double* const* next_ptr, int32_t out_dtype, uint32_t flags, void* out,
+                         const int64_t* out_off, int64_t out_rows, void* stream) {
+    if (n_clips < 0 || out_rows < 0) return FRAD_E_INVALID;
+    if (n_clips == 0) return FRAD_OK;
+    if (!valid_pcm_dtype(out_dtype) || N < 1 || C < 1) return FRAD_E_INVALID;
+    if (overlap_ratio != 0 && (overlap_ratio < 2 || overlap_ratio > 256)) return FRAD_E_INVALID;
+    if (out_rows == 0) return FRAD_OK;                         // every clip is empty: no rows, and no fragment changes hands
+    if (!frames || !clip_frame0 || !out_off || !out) return FRAD_E_INVALID;
+    const int cut = overlap_ratio ? (int)((long long)N * (overlap_ratio - 1) / overlap_ratio) : N;     // decoder.py:44
+    if (cut < 1) return FRAD_E_INVALID;                        // (N = 1 with a ratio: a frame that keeps no row cannot own out_rows > 0)
+    const int kind = out_dtype >> 3, lg = (out_dtype >> 1) & 3, be = out_dtype & 1, raw = (flags & FRAD_RAW_BE_INTS) ? 1 : 0;
+    const long long total = (long long)out_rows * C, per_block = 256LL * (16 >> lg) * CLIPS_K;
+    long long blocks = (total + per_block - 1) / per_block;
+    if (blocks > 16384) blocks = 16384;
+    if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks), blk(256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned char* o = static_cast<unsigned char*>(out);
+    const double* hann = nullptr;                              // (no overlap: cut = N, nothing is faded, nothing is carried)
+    if (N > cut) if (const int rc = hann_table(N - cut, &hann)) return rc;
+#define GO(K, L) hipLaunchKernelGGL((k_clips_carry<K, L>), grid, blk, 0, s, frames, clip_frame0, (long long)n_clips, N, C, cut, prev_ptr, next_ptr, \
+                                    hann, o, out_off, (long long)out_rows, be, raw)
     switch (kind * 4 + lg) {
         case 0: GO(0, 0); break; case 1: GO(0, 1); break; case 2: GO(0, 2); break; case 3: GO(0, 3); break;
         case 4: GO(1, 0); break; case 5: GO(1, 1); break; case 6: GO(1, 2); break; case 7: GO(1, 3); break;

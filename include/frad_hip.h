@@ -404,6 +404,31 @@ int frad_clips_window_add(const double* frames, const int64_t* clip_f0, const in
                           const int64_t* skip, const int32_t* valid, const int64_t* dst_row, int32_t out_dtype, uint32_t flags, void* out,
                           const int64_t* out_off, int64_t out_rows, void* stream);
 
+/* frad_clips_carry_add == frad_p1_overlap_add_pcm for n_clips live streams in one pass: every clip is the next run of whole
+ * frames of a stream that is still arriving, so it starts from the fragment the stream carried in and ends in the fragment it
+ * carries out, not in a flush (all arrays in device memory).  frames, clip_frame0, N, C, overlap_ratio, out_dtype, flags, out,
+ * out_off, out_rows and stream are frad_clips_overlap_add's, with the same legal values; cut = N for ratio 0, else
+ * N*(ratio-1)/ratio (at least 1), L = N - cut.
+ *   out_off     clip j's span is out_off[j+1] - out_off[j] == m_j * cut sample-frames: there is no last frame of another length
+ *               and no flush fragment.  Output row f * cut + n of clip j is row n of its frame f.
+ *   prev_ptr    NULL, or n_clips pointers: prev_ptr[j] is NULL or the fragment clip j starts from, float64 [L, C], 8-byte
+ *               aligned.  A row is faded when L > 0, n < L and either f > 0 or the clip has a fragment: against row cut + n of
+ *               frame f - 1, or row n of the fragment, as x = x * w[n]; x = x + p * w[L-1-n] (a rounded multiply, then a rounded
+ *               add) with the library's host-computed table w = hanning_in_overlap(L).  These are frad_p1_overlap_add_pcm's bits
+ *               for the same frames and prev_tail; a clip without a fragment is not faded in its first frame.
+ *   next_ptr    NULL, or n_clips pointers: when m_j > 0, L > 0 and next_ptr[j] is not NULL, rows [cut, N) of clip j's last frame
+ *               are copied there, bits unchanged: float64 [L, C] whatever out_dtype is.  A clip with m_j == 0 writes nothing
+ *               anywhere, so its pending fragment stays pending.  next_ptr[j] must not alias frames or any prev_ptr[i]: the
+ *               caller double-buffers.  With ratio 0 both tables are ignored.
+ * Nothing outside the spans and the named fragments is written, nothing beyond min(out_rows, out_off[n_clips]) sample-frames,
+ * and sample-frames before out_off[0] are left alone.  No LDS, no scratch memory.
+ * The tables are the caller's to check (core.clips_carry_add does).  FRAD_E_INVALID for N, C, the ratio, the dtype, negative
+ * counts and, with rows to write, a null frames, clip_frame0, out_off or out; FRAD_OK without a launch for n_clips == 0 (whatever
+ * the other arguments are) and for out_rows == 0 (every clip is empty then).                                                 */
+int frad_clips_carry_add(const double* frames, const int64_t* clip_frame0, int64_t n_clips, int32_t N, int32_t C, int32_t overlap_ratio,
+                         const double* const* prev_ptr, double* const* next_ptr, int32_t out_dtype, uint32_t flags, void* out,
+                         const int64_t* out_off, int64_t out_rows, void* stream);
+
 /* frad_clips_resample: polyphase sample-rate conversion of many ragged float64 spans in one pass, with frad_clips_window_add's
  * output side (all arrays in device memory).  The arithmetic is scipy.signal.resample_poly's with default arguments (zero
  * extension, Kaiser beta = 5): with M = max(up, down) and half_len = 10 * M the caller computes, in float64,
