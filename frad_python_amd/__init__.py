@@ -15,7 +15,7 @@ from .repairer import Repairer  # noqa: F401
 from .batch import decode_batch, BatchResult, encode_batch, EncodeBatchResult  # noqa: F401
 from .window import StreamIndex, WindowResult, decode_windows  # noqa: F401
 from .spectral import Spectral  # noqa: F401
-from .pool import DecoderPool, PoolResult  # noqa: F401
+from .pool import DecoderPool, EncoderPool, PoolResult  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "EncodeResult", "DecodeResult", "Repairer", "decode_batch", "BatchResult", "encode_batch", "EncodeBatchResult",
-           "StreamIndex", "WindowResult", "decode_windows", "Spectral", "DecoderPool", "PoolResult", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]
+           "StreamIndex", "WindowResult", "decode_windows", "Spectral", "DecoderPool", "EncoderPool", "PoolResult", "ASFH", "AVAILABLE", "BIT_DEPTHS", "SEGMAX", "profiles"]

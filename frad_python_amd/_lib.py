@@ -59,6 +59,8 @@ SYMBOLS = {
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_int32, c_void_p,
                                     c_void_p]),
     "frad_clips_frame_cut": (STATUS, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "frad_clips_carry_cut": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
     "frad_p1_golomb_bound": (c_size_t, [c_int32, c_int32]),
     "frad_p1_golomb_encode": (STATUS, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "frad_rows_compact": (STATUS, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

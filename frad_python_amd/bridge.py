@@ -21,6 +21,8 @@ The seam is duck-typed (no base class); a bridge is whatever has the methods its
     and ``rs_encode_crc16`` for ECC.  Optional: ``lossless_encode_stream``.
   * encode_batch: the Encoder's methods, called once per group of frames (``lossless_encode_stream`` is not optional here); optional ``clips_join`` + ``clips_frame_cut`` (the
     clips stay on the device and one launch cuts every frame; without them the cut is numpy slicing in batch.py).
+  * EncoderPool: encode_batch's methods; optional ``clips_join`` + ``clips_carry_cut`` (the members' remainders stay on the device
+    and one launch cuts a tick's frames; without them ``pool.clips_carry_cut_host`` slices in numpy).
   * Repairer: ``scan_lib``, ``rs_repair``, ``rs_encode``.
 ``p1_encode`` and ``p1_decode`` move the bare integers (tests and tools)."""
 from __future__ import annotations
@@ -426,6 +428,23 @@ class HipBridge:
         """core.clips_frame_cut: fixed-length frame rows out of the joined clips, one launch -> device uint8 [rows, row_len * step],
         which the encode methods above take in place of host bytes"""
         return self.core.clips_frame_cut(src, row_src, row_valid, row_len, step)
+
+    def clips_carry_cut(self, carry: list, src, src_off, row_clip, row_at, row_len: int, step: int, next_at):
+        """The frame rows and the remainders of many live streams in one launch (core.clips_carry_cut: EncoderPool).  ``carry``:
+        per clip None or what the stream carried in, a device uint8 tensor of whole sample-frames; ``src``: the chunks that just
+        arrived, joined (``clips_join``), clip j's at sample-frames ``src_off[j]:src_off[j + 1]``.  -> (rows, next): ``rows``
+        device uint8 [n_rows, row_len * step]; ``next[j]`` is clip j's sample-frames from ``next_at[j]`` on, on the device -- a
+        view of one block that this call allocates, so it never is a buffer that ``carry`` names."""
+        t = self.torch
+        so = np.asarray(src_off, np.int64).reshape(-1)
+        have = np.diff(so) + np.array([0 if c is None else c.numel() // step for c in carry], np.int64)
+        off = np.zeros(len(carry) + 1, np.int64)
+        np.cumsum((have - np.asarray(next_at, np.int64)) * step, out=off[1:])
+        if (np.diff(off) < 0).any():
+            raise ValueError("0 <= next_at[j] <= the clip's sample-frames")
+        block = t.empty(int(off[-1]), dtype=t.uint8, device=self.device)
+        nxt = [block[int(off[j]):int(off[j + 1])] for j in range(len(carry))]
+        return self.core.clips_carry_cut(carry, src, so, row_clip, row_at, row_len, step, next_at, nxt), nxt
 
     def p1_decode(self, q: np.ndarray, tq: np.ndarray, N, C, bits, srate) -> np.ndarray:
         t = self.torch

@@ -1215,6 +1215,99 @@ def clips_frame_cut(src: torch.Tensor, row_src, row_valid, row_len: int, step: i
     return out
 
 
+def clips_carry_cut(carry, src: torch.Tensor, src_off, row_clip, row_at, row_len: int, step: int, next_at=None, nxt=None) -> torch.Tensor:
+    """``clips_frame_cut`` for clips that are pieces of live streams, and their remainders, in one launch (frad_clips_carry_cut).
+
+    Clip j's sample-frames are ``carry[j]`` (None, or a 1-D uint8 device tensor of whole sample-frames: what the stream carried
+    over) followed by sample-frames ``src_off[j]:src_off[j + 1]`` of ``src`` (1-D uint8: the chunks that just arrived, joined);
+    ``step`` = itemsize * channels bytes per sample-frame.  Row r of the result is ``row_len`` sample-frames of clip
+    ``row_clip[r]`` from its sample-frame ``row_at[r]`` on -- in the carry, in the chunk or across the seam.  ``nxt``: None, or per
+    clip None or a 1-D uint8 device tensor that takes the clip's sample-frames from ``next_at[j]`` to its end, exactly that
+    long; it must not overlap ``src`` or any carry.  Returns uint8 [n_rows, row_len * step], the contiguous block the
+    ``*_analogue_batch`` operators read with ``frame_stride = row_len``.  Every table is host integers and is checked here,
+    before anything is uploaded or launched."""
+    if row_len < 1 or step < 1:
+        raise ValueError(f"bad geometry: row_len={row_len} step={step}")
+    so = np.ascontiguousarray(src_off, np.int64).reshape(-1)
+    n_clips = so.size - 1
+    if n_clips < 0 or len(carry) != n_clips:
+        raise ValueError("src_off needs n_clips + 1 entries and carry one per clip")
+    rc = np.ascontiguousarray(row_clip, np.int32).reshape(-1)
+    ra = np.ascontiguousarray(row_at, np.int64).reshape(-1)
+    n_rows = rc.size
+    if ra.size != n_rows:
+        raise ValueError("row_clip and row_at need one entry per row")
+    _require_frame_count(n_rows, "rows")
+    _require_frame_count(n_clips, "clips")
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError("src must be a 1-D uint8 tensor")
+    if so[0] < 0 or (np.diff(so) < 0).any() or so[-1] > src.numel() // step:
+        raise ValueError(f"src_off must not decrease and must stay inside src ({src.numel() // step} sample-frames)")
+    clen = np.zeros(max(n_clips, 1), np.int32)
+    ptrs = np.zeros((2, max(n_clips, 1)), np.uint64)
+    for j, c in enumerate(carry):
+        if c is None:
+            continue
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 1 or c.numel() % step:
+            raise ValueError(f"carry[{j}] must be a 1-D uint8 tensor of whole sample-frames")
+        clen[j] = c.numel() // step
+    have = clen[:n_clips].astype(np.int64) + np.diff(so)
+    if n_rows:
+        if ((rc < 0) | (rc >= n_clips)).any():
+            raise ValueError("row_clip names a clip that is not there")
+        if ((ra < 0) | (ra > have[rc] - row_len)).any():         # (not ra + row_len > have: that sum can wrap)
+            raise ValueError("a row does not end inside its clip")
+    na = np.zeros(max(n_clips, 1), np.int64)
+    if nxt is not None:
+        if next_at is None or len(nxt) != n_clips or len(next_at) != n_clips:
+            raise ValueError("nxt and next_at need one entry per clip")
+        na[:n_clips] = np.ascontiguousarray(next_at, np.int64).reshape(-1)
+        if ((na[:n_clips] < 0) | (na[:n_clips] > have)).any():
+            raise ValueError("0 <= next_at[j] <= the clip's sample-frames")
+        for j, t in enumerate(nxt):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != (have[j] - na[j]) * step:
+                raise ValueError(f"nxt[{j}] must be a 1-D uint8 tensor of {(have[j] - na[j]) * step} bytes")
+    # ---- the device's side: everything on one device, no remainder over anything that is read
+    _require_device_tensor(src, "src")
+    device = src.device
+    spans = [(src.data_ptr(), src.numel())] if src.numel() else []
+    for j, c in enumerate(carry):
+        if c is not None and c.numel():
+            _require_device_tensor(c, f"carry[{j}]")
+            if c.device != device:
+                raise ValueError("the carries must live on the device of src")
+            ptrs[0, j] = c.data_ptr()
+            spans.append((c.data_ptr(), c.numel()))
+    if nxt is not None:
+        spans.sort()
+        starts = np.array([s for s, _ in spans], np.uint64)
+        ends = np.array([s + n for s, n in spans], np.uint64)
+        for j, t in enumerate(nxt):
+            if t is None or not t.numel():
+                continue
+            _require_device_tensor(t, f"nxt[{j}]")
+            if t.device != device:
+                raise ValueError("the remainders must live on the device of src")
+            ptrs[1, j] = a = t.data_ptr()
+            if starts.size and ((starts < np.uint64(a + t.numel())) & (ends > np.uint64(a))).any():
+                raise ValueError(f"nxt[{j}] overlaps src or a carry")
+    out = torch.empty((n_rows, row_len * step), dtype=torch.uint8, device=device)
+    if n_clips == 0 or (n_rows == 0 and not ptrs[1].any()):
+        return out
+    # the seven tables in one upload: int64 carry_ptr | src_off | row_at | next_at | next_ptr, int32 carry_len | row_clip
+    parts = [ptrs[0, :n_clips], so, ra, na[:n_clips], ptrs[1, :n_clips], clen[:n_clips], rc]
+    dev = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).view(np.uint8) for a in parts])).to(device)
+    at = np.cumsum([0] + [a.nbytes for a in parts])
+    p = [dev.data_ptr() + int(o) for o in at[:-1]]
+    base = src.data_ptr() if src.numel() else dev.data_ptr()    # (every span empty: nothing is read through it)
+    with torch.cuda.device(device):
+        _lib.load().clips_carry_cut(p[0], p[5], base, p[1], n_clips, p[6], p[2], n_rows, row_len, step, out.data_ptr() if n_rows else 0,
+                                    p[3], p[4] if nxt is not None else 0, _stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # raw DEFLATE inflate (frad_inflate_raw): the zlib.decompress(frad, wbits=-15) of profile1.py:59 / profile2.py:61-64
 # ---------------------------------------------------------------------------------------------

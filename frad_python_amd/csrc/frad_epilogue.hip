@@ -15,7 +15,9 @@
 //                     one (frad_clips_carry_add: DecoderPool, pool.py).
 //   k_clips_cut       the Encoder's frame cut for many clips in one launch: fixed-length rows gathered from one buffer
 //                     (frad_clips_frame_cut).
-//   frad_asfh_scan    host code: walks a FrAD byte stream once and fills a table of frames (tools/asfh.py:98-134,
+//   k_clips_carry_cut k_clips_cut for clips that are pieces of live streams: rows gathered from a carried remainder and the
+//                     chunk that just arrived, and the next remainder written (frad_clips_carry_cut: EncoderPool, pool.py).
+//   frad_asfh_scan   host code: walks a FrAD byte stream once and fills a table of frames (tools/asfh.py:98-134,
 //                     decoder.py:82-106) so that the Python decoder no longer parses headers frame by frame.
 #include <atomic>
 #include "frad_p1.hpp"
@@ -512,6 +514,100 @@ __global__ void __launch_bounds__(256) k_clips_cut(const unsigned char* __restri
     }
 }
 
+// frad_clips_carry_cut: k_clips_cut for clips that are pieces of live streams.  A clip's sample-frames are a virtual sequence V
+// of two segments -- what the stream carried over from its last tick, then the chunk that just arrived (a span of one joined
+// buffer) -- and every row is whole, so there is no padding.  The launch keeps k_clips_cut's shape: 16-byte stores at aligned
+// addresses of `out`, one division finds a chunk's row, a chunk inside one segment of one row is one unaligned 16-byte load and
+// one store, and only a chunk that straddles a row end or the seam is put together byte by byte.  Behind the rows the same
+// launch copies every clip's remainder V[next_at, have) to next_ptr[j]: a block takes every gridDim.x-th clip and moves it the
+// same way (aligned 16-byte stores, byte edges) -- the pool keeps a remainder below one row, so a clip is a few KiB at most.
+struct CarrySeg {                                              // V[p] = p < cb ? carry[p] : chunk[p - cb], p in bytes
+    const unsigned char* carry;
+    const unsigned char* chunk;
+    long long cb;
+};
+__device__ __forceinline__ uint32_t seg_byte(const CarrySeg& s, long long p) { return p < s.cb ? s.carry[p] : s.chunk[p - s.cb]; }
+__device__ __forceinline__ v4u seg_load16(const CarrySeg& s, long long p) {      // V[p, p + 16), all of it inside V
+    if (p + 16 <= s.cb) return load16_anywhere(s.carry + p);
+    if (p >= s.cb) return load16_anywhere(s.chunk + (p - s.cb));
+    v4u q = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) q[k >> 2] |= seg_byte(s, p + k) << (8 * (k & 3));
+    return q;
+}
+__global__ void __launch_bounds__(256) k_clips_carry_cut(const unsigned char* const* __restrict__ carry_ptr, const int32_t* __restrict__ carry_len,
+                                                         const unsigned char* __restrict__ src, const int64_t* __restrict__ src_off,
+                                                         long long n_clips, const int32_t* __restrict__ row_clip,
+                                                         const int64_t* __restrict__ row_at, long long n_rows, long long rb, int step,
+                                                         unsigned char* __restrict__ out, const int64_t* __restrict__ next_at,
+                                                         unsigned char* const* __restrict__ next_ptr) {
+    auto seg_of = [&](long long j) {
+        CarrySeg s;
+        s.cb = (long long)carry_len[j] * step;
+        s.carry = s.cb > 0 ? carry_ptr[j] : nullptr;
+        s.chunk = src + src_off[j] * step;
+        return s;
+    };
+    const long long total = n_rows * rb;
+    const long long head = (long long)(reinterpret_cast<uintptr_t>(out) & 15);
+    const long long n_chunks = total > 0 ? (total + head + 15) >> 4 : 0;
+    const bool small = total + 16 <= 0xffffffffLL;
+    const long long tile = 256LL * CUT_K;
+    for (long long c0 = (long long)blockIdx.x * tile; c0 < n_chunks; c0 += (long long)gridDim.x * tile) {
+#pragma unroll 1
+        for (int it = 0; it < CUT_K; ++it) {
+            const long long c = c0 + (long long)it * 256 + threadIdx.x;
+            if (c >= n_chunks) break;
+            const long long o = 16 * c - head;                 // < 0 only for chunk 0 of a misaligned output
+            const long long lo = o < 0 ? 0 : o, hi = o + 16 > total ? total : o + 16;
+            long long r = small ? (long long)((uint32_t)lo / (uint32_t)rb) : lo / rb;
+            long long w = lo - r * rb;                         // the chunk's first byte inside row r
+            CarrySeg s = seg_of(row_clip[r]);
+            long long p = row_at[r] * step + w;                // ... and inside the clip's V
+            if (hi - lo == 16 && w + 16 <= rb) {
+                *FRAD_GPTR(v4u, out + o) = seg_load16(s, p);
+                continue;
+            }
+            v4u q = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const long long b = o + k;
+                if (b < lo || b >= hi) continue;
+                if (w == rb) {                                 // the next row (rb >= 1: at most one step per byte)
+                    ++r; w = 0;
+                    s = seg_of(row_clip[r]);
+                    p = row_at[r] * step;
+                }
+                q[k >> 2] |= seg_byte(s, p) << (8 * (k & 3));
+                ++w; ++p;
+            }
+            if (hi - lo == 16) *FRAD_GPTR(v4u, out + o) = q;
+            else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (o + k >= lo && o + k < hi) out[o + k] = (unsigned char)(q[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+    }
+    if (next_ptr == nullptr) return;
+    for (long long j = blockIdx.x; j < n_clips; j += gridDim.x) {      // the remainders: plain copies, bits unchanged
+        unsigned char* const dst = next_ptr[j];
+        if (dst == nullptr) continue;
+        const CarrySeg s = seg_of(j);
+        const long long p0 = next_at[j] * step;
+        const long long n = s.cb + (src_off[j + 1] - src_off[j]) * step - p0;
+        if (n <= 0) continue;
+        long long hd = (16 - (long long)(reinterpret_cast<uintptr_t>(dst) & 15)) & 15;      // bytes in front of the first aligned store
+        if (hd > n) hd = n;
+        const long long nq = (n - hd) >> 4, edge = n - 16 * nq;                             // edge: hd in front, the rest behind (< 31)
+        for (long long i = threadIdx.x; i < nq; i += blockDim.x) *FRAD_GPTR(v4u, dst + hd + 16 * i) = seg_load16(s, p0 + hd + 16 * i);
+        for (long long i = threadIdx.x; i < edge; i += blockDim.x) {
+            const long long at = i < hd ? i : 16 * nq + i;
+            dst[at] = (unsigned char)seg_byte(s, p0 + at);
+        }
+    }
+}
+
 template <int SRC>
 int launch_from_f64(int dtype, const unsigned char* in, unsigned char* out, long long n, const Geom& g, hipStream_t s) {
     const int kind = dtype >> 3, lg = (dtype >> 1) & 3, be = dtype & 1;
@@ -764,6 +860,28 @@ int frad_clips_frame_cut(const void* src, const int64_t* row_src, const int32_t*
     hipLaunchKernelGGL(k_clips_cut, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char*>(src), row_src, row_valid, (long long)n_rows, rb, (int)step,
                        static_cast<unsigned char*>(out));
+    FRAD_HIPCHK(hipGetLastError());
+    return FRAD_OK;
+}
+
+int frad_clips_carry_cut(const void* const* carry_ptr, const int32_t* carry_len, const void* src, const int64_t* src_off,
+                         int64_t n_clips, const int32_t* row_clip, const int64_t* row_at, int64_t n_rows, int32_t row_len,
+                         int32_t step, void* out, const int64_t* next_at, void* const* next_ptr, void* stream) {
+    if (step < 1 || row_len < 1 || n_clips < 0 || n_rows < 0) return FRAD_E_INVALID;
+    if (n_clips == 0) return FRAD_OK;
+    const long long rb = (long long)row_len * step;
+    if (!carry_ptr || !carry_len || !src || !src_off || (next_ptr && !next_at)) return FRAD_E_INVALID;
+    if (n_rows > 0 && (!row_clip || !row_at || !out || n_rows > (0x7fffffffffffffffLL - 32) / rb)) return FRAD_E_INVALID;
+    if (n_rows == 0 && !next_ptr) return FRAD_OK;              // no row and no remainder: nothing to write
+    const long long chunks = n_rows ? (n_rows * rb + 30) / 16 : 0, per_block = 256LL * CUT_K;      // (an upper bound: head <= 15)
+    long long blocks = (chunks + per_block - 1) / per_block;
+    const long long for_clips = next_ptr ? (n_clips < 4096 ? n_clips : 4096) : 0;                  // a block per remainder
+    if (blocks < for_clips) blocks = for_clips;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_clips_carry_cut, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const unsigned char* const*>(carry_ptr), carry_len, static_cast<const unsigned char*>(src), src_off,
+                       (long long)n_clips, row_clip, row_at, (long long)n_rows, rb, (int)step, static_cast<unsigned char*>(out), next_at,
+                       reinterpret_cast<unsigned char* const*>(next_ptr));
     FRAD_HIPCHK(hipGetLastError());
     return FRAD_OK;
 }

@@ -1,4 +1,5 @@
-"""``DecoderPool``: many live streams decoded chunk by chunk, one device pass per tick.
+"""``DecoderPool`` and ``EncoderPool``: many live streams decoded (encoded) chunk by chunk, one device pass per tick.  The decode
+side first; the encode side is described where it begins, further down.
 
 ``Decoder`` is the streaming object, one stream each: a server that holds a few hundred of them pays a chain of launches per
 stream on every tick, each over the two or three dozen frames a chunk completes.  ``decode_batch`` and ``StreamIndex`` run every
@@ -20,10 +21,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from .backend.pcmformat import ff_format_to_numpy_type, from_f64
-from .batch import _frames
+from .backend.pcmformat import FORMAT_NAMES, ff_format_to_numpy_type, from_f64
+from .batch import _compact_payloads, _frames, _host_bytes, _lossless_rows
 from .decoder import Decoder, DecodeResult
+from .encoder import Encoder, EncodeResult
 from .fourier import BIT_DEPTHS
+from .fourier.profiles import COMPACT, compact
 from .frames import DEFLATED, Damaged, repair
 
 
@@ -55,8 +58,9 @@ def clips_carry_host(frames, clip_frame0, N, C, ratio, prev=None, out_format=Non
 
 
 class PoolResult(dict):
-    """One tick: ``res[h]`` is the ``DecodeResult`` (pcm, srate, frames, crit) of handle h; ``fallback``: the handles whose tick
-    the per-stream path decoded, in the order of the tick's dict."""
+    """One tick: ``res[h]`` is the ``DecodeResult`` (pcm, srate, frames, crit) of handle h -- from an ``EncoderPool`` its
+    ``EncodeResult`` (buf, samples); ``fallback``: the handles whose tick the per-stream path decoded (encoded), in the order of
+    the tick's dict."""
 
     def __init__(self):
         super().__init__()
@@ -250,3 +254,234 @@ class DecoderPool:
             t, raw = self.bridge.torch, np.ascontiguousarray(r.pcm)
             r.pcm = t.from_numpy(raw if self.out_format is None or raw.dtype == np.float64 else raw.view(np.uint8).reshape(-1)).to(self.bridge.device)
         return r
+
+
+# ======================================================================================================================
+# EncoderPool: the encode side's streaming shape.  ``Encoder`` is one stream each: per tick and stream it uploads
+# its whole buffer -- the overlap carry again every time -- and runs a chain of launches over the two or three frames a chunk
+# completes.  ``encode_batch`` runs every stage once, but wants its clips whole.  Here every member keeps an ``Encoder``'s own
+# state, with the remainder behind its last whole frame on the device; one launch of ``frad_clips_carry_cut`` gathers the frames a
+# tick completes -- each from what the member carried over and the chunk that just arrived -- and writes the next remainders,
+# and the frames of all members go through ``batch._lossless_rows`` / ``_compact_payloads`` / ``Encoder._emit_all`` once.
+# ``res[h]`` is, byte for byte, what an ``Encoder`` of its own returns from ``process(chunk)`` for the same chunk sequence.
+def clips_carry_cut_host(carry: list, src, src_off, row_clip, row_at, row_len: int, step: int, next_at):
+    """What ``HipBridge.clips_carry_cut`` computes, by numpy slicing, for a bridge without it.  ``carry``: per clip None or a
+    uint8 ndarray of whole sample-frames; ``src``: the joined chunks, uint8.  -> (ndarray [n_rows, row_len * step], next):
+    ``next[j]`` clip j's bytes from sample-frame ``next_at[j]`` on, an array of its own."""
+    src = np.frombuffer(src, np.uint8) if not isinstance(src, np.ndarray) else src.reshape(-1)
+    none = np.zeros(0, np.uint8)
+    seq = [np.concatenate([none if c is None else np.asarray(c, np.uint8).reshape(-1), src[int(src_off[j]) * step:int(src_off[j + 1]) * step]])
+           for j, c in enumerate(carry)]
+    out = np.empty((len(row_clip), row_len * step), np.uint8)
+    for r, (c, at) in enumerate(zip(row_clip, row_at)):
+        row = seq[int(c)][int(at) * step:(int(at) + row_len) * step]
+        if at < 0 or row.size != row_len * step:
+            raise ValueError("a row does not end inside its clip")
+        out[r] = row
+    if any(not 0 <= int(a) * step <= seq[j].size for j, a in enumerate(next_at)):
+        raise ValueError("0 <= next_at[j] <= the clip's sample-frames")
+    return out, [seq[j][int(a) * step:].copy() for j, a in enumerate(next_at)]
+
+
+class _EncMember(Encoder):
+    """An ``Encoder`` whose buffer lives with the pool between plain ticks.  ``held``: its whole sample-frames behind the last
+    frame written (a device uint8 tensor behind a bridge that cuts on the device, an ndarray otherwise; None: none), and the
+    inherited ``buffer`` the bytes behind them -- fewer than a sample-frame while ``held`` is there, the ``Encoder``'s whole buffer
+    after a fallback tick or a flush.  The ``Encoder``'s buffer is ``held ++ buffer`` at all times."""
+    held = None
+
+    def __init__(self, pool):
+        pool._settings(self)
+        self.pool = pool
+
+    def to_host(self):
+        if self.held is not None:
+            self.buffer, self.held = _host_bytes(self.held) + self.buffer, None
+            self.pool.carry_downloads += 1
+
+    def flush(self) -> EncodeResult:
+        self.to_host()
+        return Encoder.flush(self)
+
+
+class _Tick:
+    """One member's part of a tick that brings whole sample-frames: ``pieces`` [(bytes-like or device tensor, bytes taken)] go up,
+    ``new`` sample-frames in all; ``tail``: the bytes left behind them; ``k`` whole frames out of ``have`` sample-frames."""
+    __slots__ = ("h", "m", "pieces", "new", "tail", "have", "k", "samples", "uploads")
+
+
+class EncoderPool:
+    def __init__(self, profile: int, srate: int, channels: int, bit_depth: int, frame_size: int, pcm_format: str, *,
+                 overlap_ratio: int = 0, loss_level: float = 0.5, little_endian: bool = False, ecc_ratio=None,
+                 allow_profile2: bool = False, device_deflate: bool = False, max_batch_bytes: int = 1 << 30, bridge=None):
+        """The arguments mean what ``encode_batch``'s mean, clamping included, and what the ``Encoder`` refuses is a ``ValueError``;
+        one pool has one setting.  ``max_batch_bytes``: a tick whose gathered frames would exceed it is cut into chunks of whole
+        members."""
+        checks = (lambda: None if (profile == 2 and allow_profile2) else Encoder.verify_profile(profile),
+                  lambda: Encoder.verify_srate(profile, srate), lambda: Encoder.verify_channels(profile, channels),
+                  lambda: Encoder.verify_bit_depth(profile, bit_depth), lambda: Encoder.verify_frame_size(profile, frame_size))
+        for check in checks:
+            e = check()
+            if e is not None:
+                raise ValueError(e)
+        if str(pcm_format).lower() not in FORMAT_NAMES:         # (the Encoder leaves the process on this one)
+            raise ValueError(f"Invalid format: {pcm_format}")
+        if bridge is None:
+            from .bridge import HipBridge
+            bridge = HipBridge()
+        self.bridge, self.max_batch_bytes = bridge, max_batch_bytes
+        self._args = (profile, srate, channels, bit_depth, frame_size, pcm_format)
+        self._kw = dict(allow_profile2=allow_profile2, allow_ecc=ecc_ratio is not None, device_deflate=device_deflate)
+        self._set = (overlap_ratio, loss_level, little_endian, ecc_ratio)
+        self._enc = Encoder.__new__(Encoder)                    # the settings, the header writer and the bridge of every tick
+        self._settings(self._enc)
+        enc = self._enc
+        is_compact = profile in COMPACT
+        self.n_eff = compact.get_samples_min_ge(enc.fsize) if is_compact else enc.fsize
+        ratio = enc.asfh.overlap_ratio
+        self.cut = self.n_eff * (ratio - 1) // ratio if (is_compact and ratio > 1) else self.n_eff      # Encoder.inner's hop
+        self.step = enc.pcm_format.itemsize * channels
+        depths = BIT_DEPTHS[profile]
+        self._idx = depths.index(enc.bit_depth if enc.bit_depth in depths else 16)
+        self._on_dev = getattr(bridge, "clips_carry_cut", None) is not None and getattr(bridge, "clips_join", None) is not None
+        self._members, self._next = {}, 0
+        self.carry_uploads = self.carry_downloads = 0          # host <-> device copies of members' buffers so far
+
+    def _settings(self, enc: Encoder):
+        """``enc`` becomes an ``Encoder`` with the pool's settings, through its constructor and setters"""
+        overlap_ratio, loss_level, little_endian, ecc_ratio = self._set
+        Encoder.__init__(enc, *self._args, bridge=self.bridge, **self._kw)
+        enc.set_overlap_ratio(overlap_ratio)
+        enc.set_loss_level(loss_level)
+        enc.set_little_endian(little_endian)
+        if ecc_ratio is not None:
+            enc.set_ecc(True, ecc_ratio)
+
+    # ------------------------------------------------------------------------------------------------------------ handles
+    def open(self) -> int:
+        """A new stream -> its handle; handles are never reused"""
+        h, self._next = self._next, self._next + 1
+        self._members[h] = _EncMember(self)
+        return h
+
+    def flush(self, h) -> EncodeResult:
+        """The ``Encoder``'s ``flush()`` of stream h, by the per-stream path: its remainder comes down first"""
+        return self._members[h].flush()
+
+    def close(self, h) -> EncodeResult:
+        """``flush(h)``, and the handle is forgotten"""
+        r = self.flush(h)
+        del self._members[h]
+        return r
+
+    # --------------------------------------------------------------------------------------------------------------- a tick
+    def process(self, chunks: dict) -> PoolResult:
+        """One tick: ``chunks[h]`` (bytes-like, or a 1-D device uint8 tensor of whole sample-frames; may be empty) is appended
+        to stream h; a handle that is not in the dict is not touched.  -> ``PoolResult`` of ``EncodeResult``s.  No member
+        changes before every launch of the tick has succeeded: after a device error the same call can be made again."""
+        members = {h: self._members[h] for h in chunks}         # (KeyError before any stream has moved)
+        step, n_eff, cut = self.step, self.n_eff, self.cut
+        for chunk in chunks.values():
+            if hasattr(chunk, "numel"):
+                if chunk.dim() != 1 or chunk.element_size() != 1:
+                    raise TypeError("a device chunk must be a 1-D uint8 tensor of the PCM's bytes")
+                if chunk.numel() % step:
+                    raise ValueError(f"a device chunk must hold whole sample-frames of {step} bytes")
+        res, ticks, quiet = PoolResult(), [], {}
+        for h, chunk in chunks.items():
+            m, res[h] = members[h], EncodeResult(b"", 0)
+            pend = m.buffer
+            on_dev = hasattr(chunk, "numel")
+            if not on_dev and not isinstance(chunk, bytes):
+                chunk = bytes(chunk)
+            n = chunk.numel() if on_dev else len(chunk)
+            new = (len(pend) + n) // step
+            left = len(pend) + n - new * step
+            t = _Tick()
+            if on_dev:
+                head = min(len(pend), new * step)
+                t.pieces = [(pend, head), (chunk, new * step - head)]
+                t.tail = (pend + _host_bytes(chunk[max(0, n - left):]))[-left:] if left else b""     # (fewer than `step` bytes come down)
+            else:
+                data = pend + chunk if pend else chunk
+                t.pieces, t.tail = [(data, new * step)], data[new * step:]
+            if not new:                                         # no whole sample-frame arrived: nothing to cut or to carry
+                quiet[h] = t.tail
+                continue
+            held = 0 if m.held is None else len(m.held) // step
+            t.h, t.m, t.new, t.have, t.uploads = h, m, new, held + new, int(len(pend) >= step)
+            t.k = (t.have - n_eff) // cut + 1 if t.have >= n_eff else 0
+            t.samples = t.k * n_eff - (t.k - 1) * (n_eff - cut) - (n_eff - cut if m.have_carry else 0) if t.k else 0     # Encoder.inner
+            ticks.append(t)
+        done, deeper = [], []                                   # (a _Tick, its frames, its remainder); the ticks that fall back
+        group, size = [], 0
+        for t in ticks + [None]:
+            need = 0 if t is None else t.k * n_eff * step
+            if group and (t is None or size + need > self.max_batch_bytes):
+                while group:
+                    outs, nxt, bad = self._cut_and_encode(group)
+                    if not bad:
+                        done.extend(zip(group, outs, nxt))
+                        break
+                    deeper.extend(group[d] for d in bad)        # the frame-by-frame route of the Encoder decides their depths
+                    group = [g for d, g in enumerate(group) if d not in set(bad)]
+                group, size = [], 0
+            if t is not None:
+                group.append(t)
+                size += need
+        # ---- nothing has changed so far.  The fallback members first: each is transactional, and is put back if a later one fails
+        keep = [(t.m, t.m.buffer, t.m.held, t.m.have_carry, vars(t.m.asfh).copy()) for t in deeper]
+        counters = (self.carry_uploads, self.carry_downloads)
+        try:
+            for t in sorted(deeper, key=ticks.index):
+                t.m.to_host()
+                res[t.h] = Encoder.process(t.m, _host_bytes(chunks[t.h]))
+                res.fallback.append(t.h)
+        except BaseException:
+            for m, buffer, held, have_carry, asfh in keep:
+                m.buffer, m.held, m.have_carry = buffer, held, have_carry
+                vars(m.asfh).update(asfh)
+            self.carry_uploads, self.carry_downloads = counters
+            raise
+        for h, tail in quiet.items():
+            members[h].buffer = tail
+        for t, out, nxt in done:
+            m = t.m
+            m.buffer, m.held = t.tail, (nxt if len(nxt) else None)
+            self.carry_uploads += t.uploads
+            if t.k:
+                m.have_carry = n_eff > cut
+                m._head(self._idx, n_eff)                       # the header writer as its own Encoder leaves it
+            res[t.h] = EncodeResult(out, t.samples)
+        return res
+
+    def _cut_and_encode(self, group: list):
+        """The ticks of one chunk of members: one ``clips_carry_cut`` for every frame row and every remainder, then every stage
+        once.  -> (frames per member, remainder per member, []), or (None, None, the members with a lossless frame that needs a
+        deeper format): the caller sends the rest again."""
+        br, enc, step, n_eff, cut = self.bridge, self._enc, self.step, self.n_eff, self.cut
+        pieces = [p for t in group for p in t.pieces]
+        src_off = np.zeros(len(group) + 1, np.int64)
+        np.cumsum([t.new for t in group], out=src_off[1:])
+        first = np.zeros(len(group) + 1, np.int64)              # member j's frames are rows first[j] : first[j + 1]
+        np.cumsum([t.k for t in group], out=first[1:])
+        M = int(first[-1])
+        row_clip = np.repeat(np.arange(len(group), dtype=np.int32), [t.k for t in group])
+        row_at = np.concatenate([cut * np.arange(t.k, dtype=np.int64) for t in group])
+        carry, next_at = [t.m.held for t in group], [t.k * cut for t in group]
+        if self._on_dev:
+            src = br.clips_join([c for c, _ in pieces], [n for _, n in pieces])
+            block, nxt = br.clips_carry_cut(carry, src, src_off, row_clip, row_at, n_eff, step, next_at)
+        else:
+            src = np.frombuffer(b"".join(_host_bytes(c)[:n] for c, n in pieces), np.uint8)
+            block, nxt = clips_carry_cut_host(carry, src, src_off, row_clip, row_at, n_eff, step, next_at)
+            block = block.tobytes()
+        if not M:
+            return [b""] * len(group), nxt, []
+        if enc.asfh.profile not in COMPACT:
+            take, bad = _lossless_rows(enc, block, M, n_eff)
+            if bad is not None:
+                return None, None, [j for j in range(len(group)) if any(bad[first[j]:first[j + 1]])]
+            return [take(int(first[j]), t.k) if t.k else b"" for j, t in enumerate(group)], nxt, []
+        made = enc._emit_all([(p, self._idx, n_eff) for p in _compact_payloads(enc, block, M, n_eff)])
+        return [b"".join(made[first[j]:first[j + 1]]) for j in range(len(group))], nxt, []

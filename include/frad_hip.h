@@ -527,6 +527,30 @@ int frad_clips_spectrum(const double* const* src_ptr, const int32_t* valid, int6
 int frad_clips_frame_cut(const void* src, const int64_t* row_src, const int32_t* row_valid, int64_t n_rows, int32_t row_len, int32_t step,
                          void* out, void* stream);
 
+/* frad_clips_carry_cut == frad_clips_frame_cut for clips that are pieces of live streams (all arrays in device memory).  Clip j's
+ * virtual sequence V_j is carry_len[j] sample-frames at carry_ptr[j], then the sample-frames src[src_off[j] .. src_off[j+1]) of one
+ * joined buffer; have_j is their sum.  step = itemsize * channels bytes per sample-frame (1 = u8 mono, upwards, no power of two
+ * needed), rb = row_len * step bytes per row.
+ *   out         [n_rows, row_len] sample-frames, contiguous, any alignment: row r is V_c[row_at[r] .. row_at[r] + row_len) with
+ *               c = row_clip[r] (int32 [n_rows]; row_at int64 [n_rows]).  Every row is whole -- there is no padding -- and may lie in
+ *               the carry, in the chunk or across the seam; rows of one clip overlap when the hop is smaller than row_len.  The
+ *               block frad_p{0,1,2,4}_analogue read with frame_stride = row_len.
+ *   next_ptr    NULL, or n_clips pointers: where next_ptr[j] is not NULL the bytes of V_j[next_at[j] .. have_j) are copied there,
+ *               bits unchanged (next_at int64 [n_clips]; it may be zero sample-frames, and it may begin inside the carry: a clip
+ *               without a row carries out carry ++ chunk).  next_ptr[j] must not alias out, src or any carry_ptr[i]: the caller
+ *               double-buffers.  A clip with a NULL next_ptr[j] writes nothing there.
+ *   carry_ptr   n_clips pointers; carry_ptr[j] may be NULL where carry_len[j] == 0 (int32 [n_clips] >= 0).  Carries, src and the
+ *               destinations may sit at any byte alignment.
+ *   src         never NULL (any address will do when every span is empty); src_off int64 [n_clips + 1], non-decreasing.
+ * One launch writes the rows and the remainders.  Nothing outside out's n_rows * rb bytes and the named remainders is written.
+ * No LDS, no scratch memory.
+ * The tables are the caller's to check (core.clips_carry_cut does): every row must end inside its clip's have_j, 0 <= next_at[j]
+ * <= have_j, and src_off must stay inside src.  FRAD_E_INVALID for step < 1, row_len < 1, negative counts, and a null table or
+ * buffer with something to read or write through it; FRAD_OK without a launch for n_clips == 0, and for no row and no next_ptr. */
+int frad_clips_carry_cut(const void* const* carry_ptr, const int32_t* carry_len, const void* src, const int64_t* src_off,
+                         int64_t n_clips, const int32_t* row_clip, const int64_t* row_at, int64_t n_rows, int32_t row_len,
+                         int32_t step, void* out, const int64_t* next_at, void* const* next_ptr, void* stream);
+
 /* frad_asfh_scan: HOST code (no device involved).  One pass over a FrAD byte stream from `start`: resynchronises on
  * FRM_SIGN and parses every header as ASFH.read does (tools/asfh.py:98-134; the search as decoder.py:82-90), filling
  * frames[0 .. return value).  Stops at the first header or payload that is not completely inside the buffer, at
